@@ -1,6 +1,8 @@
 """Benchmark: reachability build + all Kano checks on MI355X (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--dump-outputs DIR]
+    python bench.py --full ...      the same line plus everything measured or
+                                    checked beside the K steps (below)
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N ...
 
@@ -19,6 +21,12 @@ GPU, kano_verify_shard); the column checks combine the ranks' [OR | cross |
 NAND] bit words (3 * W u64 each) gathered by one RCCL all-gather over xGMI and
 OR-ed on the device (kano_verify_combine; RCCL has no bitwise reduction);
 strong scaling (fixed cluster).
+
+A plain run sets up, warms up, times the K steps, writes the last step's
+results with --dump-outputs and prints the line.  --full adds what takes work
+of its own: the results checked against the golden record (verified), k_rows
+alone (roofline.alone), the device's plain fill rate, the cold drop-in call,
+kano_py's recorded times and the CPU baseline.
 
 Rank 0 prints ONE JSON line.  roofline: the dominant kernel is k_rows (the
 matrix write), algorithmic bytes = 8 * rows * W (the bit matrix it writes),
@@ -74,15 +82,27 @@ def parse():
                          "(every subset test, no emission: C4's ~1e11 pairs), or off; "
                          "auto = count for C4, pairs otherwise")
     ap.add_argument("--no-shadow", action="store_true", help="same as --shadow off")
-    ap.add_argument("--cpu-baseline", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the timed steps: the results against the "
+                         "golden record, k_rows alone, the device fill rate, the cold drop-in "
+                         "call, kano_py's recorded times, the CPU baseline (each still "
+                         "switched by its own option below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's results (what the "
+                         "caller of the step receives) as DIR/<name>.npy, float64: each "
+                         "check's pod list as a 0/1 vector over the pods, policy_shadow's "
+                         "pairs and their count")
+    ap.add_argument("--cpu-baseline", type=int, default=1,
+                    help="with --full: the CPU baseline (0: none)")
     ap.add_argument("--cold", type=int, default=1,
-                    help="also time the drop-in API once on fresh objects (C2 / C3, one rank)")
+                    help="with --full: also time the drop-in API once on fresh objects "
+                         "(C2 / C3, one rank)")
     ap.add_argument("--shard-path", action="store_true",
                     help="diagnostic: the N > 1 step (shard verify + RCCL all-gather + combine) "
                          "even at one rank, e.g. under torch.distributed.run --nproc-per-node 1")
     ap.add_argument("--alone", type=int, default=5,
-                    help="k_rows launches timed alone (kano_build) after the timed region "
-                         "(roofline.alone; 0: none)")
+                    help="with --full: k_rows launches timed alone (kano_build) after the "
+                         "timed region (roofline.alone; 0: none)")
     ap.add_argument("--pipeline", type=int, default=1,
                     help="kano_set_pipeline: each step queues the next step's prologue behind a "
                          "gate the next step opens (0: off)")
@@ -92,7 +112,10 @@ def parse():
     ap.add_argument("--rank-of", type=int, default=0,
                     help="diagnostic: time rank 0's shard step of an N-rank run on one GPU "
                          "(the all-gather replaced by a local copy; not a bench line)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 class Step:
@@ -474,7 +497,7 @@ def main():
     # CU-masked stream beside the next step's build)
     eng.rows_timing(reset=True)
     eng.mfma_timing(reset=True)
-    for _ in range(args.alone):
+    for _ in range(args.alone if args.full else 0):
         eng.build()
     ra = eng.rows_timing()
     mta = eng.mfma_timing()
@@ -490,12 +513,16 @@ def main():
         dist.all_reduce(t)
         shadow_cnt = int(t.item())
     out = None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, n)
     traffic, traffic_src = (pmc_traffic(args.config, args.rank_of, info["ROWS_KERNEL"])
                             if world == 1 else (None, None))
     # the last step's results against kano_py's own outputs on this cluster
     # (tests/golden/expected/<config>.json); on row shards rank 0 checks the
     # combined column lists and the system row it owns
-    if args.rank_of > 1:
+    if not args.full:
+        verified, vdetail = None, "not checked (--full checks the results against the record)"
+    elif args.rank_of > 1:
         verified, vdetail = verify_shard_alone(args.config, cl, tables, gid, eng, step.results,
                                                r0, r1, shadow)
     else:
@@ -506,7 +533,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MIN)
         if int(t.item()) == 0 and verified is not False:
             verified, vdetail = False, "another rank's results differ from the golden"
-    box_fill = box_store_rate(torch, eng.W * 8 * max(r1 - r0, 1)) if world == 1 else None
+    box_fill = (box_store_rate(torch, eng.W * 8 * max(r1 - r0, 1))
+                if args.full and world == 1 else None)
     if rank == 0:
         out = {
             "metric": METRIC, "value": value, "unit": "pod-pairs/s", "n_gpus": world,
@@ -619,12 +647,13 @@ def main():
         }
         # (C2 / C3: kano_py's own policy_shadow list; C4's ~2.7e10 pairs fit no
         # host list, C5's matrix no host memory)
-        if args.cold and world == 1 and args.rank_of <= 1 and n <= 200_000 and shadow == "pairs":
+        if (args.full and args.cold and world == 1 and args.rank_of <= 1 and n <= 200_000
+                and shadow == "pairs"):
             out["cold_drop_in"] = cold_drop_in(cl, args.config)
-        ref = kano_py_measured(args.config)
+        ref = kano_py_measured(args.config) if args.full else None
         if ref:
             out["kano_py_measured"] = ref
-        if (args.cpu_baseline and world == 1 and args.rank_of <= 1 and n <= 200_000
+        if (args.full and args.cpu_baseline and world == 1 and args.rank_of <= 1 and n <= 200_000
                 and shadow == "pairs"):
             out["cpu_baseline"] = cpu_baseline(cl, gid, args.config)
             out["cpu_baseline"]["cpu"] = _cpu_model()
@@ -727,7 +756,12 @@ def group_main(args, torch, cl, tables, gid, shadow):
     # every member's beside it
     r0 = rows[0]
     fr = [r["achieved"] / HBM_PEAK_GBS for r in rows]
-    verified, vdetail = verify_against_golden(args.config, cl, step.results, 1, 0, 0, shadow)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, step.results, n)
+    if args.full:
+        verified, vdetail = verify_against_golden(args.config, cl, step.results, 1, 0, 0, shadow)
+    else:
+        verified, vdetail = None, "not checked (--full checks the results against the record)"
     out = {
         "metric": METRIC, "value": float(n) * n / (elapsed / args.steps), "unit": "pod-pairs/s",
         "n_gpus": N, "steps": args.steps, "warmup": args.warmup,
@@ -766,6 +800,46 @@ def group_main(args, torch, cl, tables, gid, shadow):
     eng.close()
     if verified is False:
         sys.exit(f"bench: results differ from the golden: {vdetail}")
+
+
+DUMP_MAX_ELEMS = 1 << 20     # per array: 8 MiB of float64, 6 arrays < 64 MB
+DUMP_SEED = 20240611
+
+
+POD_LISTS = ("all_reachable", "all_isolated", "user_crosscheck", "system_isolation")
+
+
+def dump_outputs(dirpath, res, n):
+    """The last timed step's results, one DIR/<name>.npy each in float64
+    (int32 indices and the count are exact in it).  The four checks return
+    lists of pod indices, whose lengths depend on the cluster (C3's
+    all_reachable is empty); each is written as its membership vector over the
+    n pods, 1.0 where the pod is in the list, so that the file has n elements
+    whatever the list holds and two builds' files compare element by element.
+    policy_shadow's (count, 2) pairs are written as they are (no file for an
+    empty list) beside policy_shadow_count.  An array of more than
+    DUMP_MAX_ELEMS elements is written as a fixed sample of its rows (sorted
+    row indices drawn once from DUMP_SEED and the row count, the same from run
+    to run)."""
+    os.makedirs(dirpath, exist_ok=True)
+    for name, v in res.items():
+        if v is None:
+            continue
+        a = np.asarray(v)
+        if name in POD_LISTS:
+            mask = np.zeros(n, dtype=np.float64)
+            mask[a.astype(np.int64)] = 1.0
+            a = mask
+        if a.ndim == 0:
+            a = a.reshape(1)
+        if a.shape[0] == 0:
+            continue
+        per_row = int(np.prod(a.shape[1:], dtype=np.int64)) if a.ndim > 1 else 1
+        keep = DUMP_MAX_ELEMS // max(1, per_row)
+        if a.shape[0] > keep:
+            rng = np.random.Generator(np.random.PCG64([DUMP_SEED, a.shape[0]]))
+            a = a[np.sort(rng.choice(a.shape[0], size=keep, replace=False))]
+        np.save(os.path.join(dirpath, f"{name}.npy"), np.asarray(a, dtype=np.float64))
 
 
 def _golden(config):

@@ -33,7 +33,7 @@ def main():
             env = dict(os.environ, KANO_TUNE=tune)
             if lib:
                 env["KANO_HIP_LIB"] = os.path.join(ROOT, lib)
-            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", a.config,
+            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", a.config,
                    "--steps", str(a.steps), "--warmup", str(a.warmup), "--cpu-baseline", "0",
                    "--cold", "0"] + a.extra.split()
             r = subprocess.run(["timeout", "-k", "10", str(a.timeout)] + cmd, env=env,

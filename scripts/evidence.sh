@@ -49,6 +49,7 @@ PY
 
 bench() {  # name, timeout, args...
   local nm=$1 to=$2; shift 2
+  set -- --full "$@"   # summ reads verified, roofline.alone, cpu_baseline, cold_drop_in
   timeout -k 10 "$to" python3 bench.py "$@" > gpurun_out/lines/$nm.json 2> gpurun_out/lines/$nm.err \
     || { echo "$nm failed"; tail -5 gpurun_out/lines/$nm.err; exit 1; }
   summ gpurun_out/lines/$nm.json "$nm"

@@ -3,6 +3,8 @@
 # Each GPU step has its own time limit; a crash / timeout / abort ends the
 # script (no further GPU step in the same call).
 set -u
+# the bench with everything beside its timed steps (golden check, k_rows alone, baselines)
+BENCH_ARGS="--full ${BENCH_ARGS:-}"
 mkdir -p gpurun_out
 stop_if_fatal() {  # $1 = exit code of a GPU step
   case "$1" in 0|1) return 0 ;; *) echo "fatal rc=$1, stopping"; exit "$1" ;; esac

@@ -180,7 +180,7 @@ def test_bench_group_line_two_members_one_device():
     env = dict(os.environ, KANO_DEVICES="0,0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full",
                         "--steps", "20", "--warmup", "3"], capture_output=True, text=True,
                        timeout=240, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
