@@ -161,6 +161,35 @@ int kano_shadow_lists(kano_ctx* ctx, int64_t n_lists, int64_t nbits, int64_t P,
  * pod of this shard has |S(i)| >= 2. */
 int kano_conflict(kano_ctx* ctx, int* raises);
 
+/* The working policy_conflict (the check algorithm.py:83-100 was written to
+ * be): emits, for this shard's pods in ascending order,
+ * every ordered pair (j,k) of policies selecting the pod, in list order,
+ * with j != k by value and allow_j and allow_k sharing no pod.  Duplicates are
+ * kept (one entry per pod, quirk Q4); the relation is symmetric, so both
+ * orders appear; an empty allow set conflicts with every other policy.
+ * mode 0 computes the pairs (fetch 2*count int32 with kano_conflict_fetch),
+ * mode 1 only counts (no flags, no compaction; kano_conflict_fetch then
+ * returns -EINVAL, as it does before any kano_conflict_pairs).  class_pairs
+ * (nullable): the pairs at row-class level, the length kano_conflict_classes
+ * writes.  The pairs and their total are the call's own: kano_shadow_fetch
+ * after an interleaved kano_conflict_pairs still returns the shadow pairs,
+ * and the other way round.  A pairs buffer that cannot be allocated returns
+ * -ENOMEM (kano_last_error) and leaves the context usable.  kano_conflict
+ * above is unchanged: it reproduces the reference's raise. */
+int kano_conflict_pairs(kano_ctx* ctx, int mode, int64_t* count, int64_t* class_pairs);
+int kano_conflict_fetch(kano_ctx* ctx, int32_t* pairs /* 2*count */);
+/* The same over explicit inputs (the arguments of kano_shadow_lists; an id
+ * outside [0, P) returns -ERANGE).  The context holds no matrix afterwards. */
+int kano_conflict_lists(kano_ctx* ctx, int64_t n_lists, int64_t nbits, int64_t P,
+                        const int64_t* soff, const int32_t* slist, const uint64_t* allow_rows,
+                        int mode, int64_t* count);
+/* Class level: row class c's conflicting (j,k) are pairs[2*off[c] ..
+ * 2*off[c+1]) (off[U] = class_pairs of kano_conflict_pairs) and members[c]
+ * pods of this shard share them.  Runs the tests itself; any of the three
+ * outputs may be NULL. */
+int kano_conflict_classes(kano_ctx* ctx, int64_t* off /* U+1 */, int32_t* pairs,
+                          int32_t* members /* U */);
+
 /* The whole verification pass in one call (the sequence kano_py's
  * sample/example.py and tests/test_basic.py run: build_matrix, then
  * all_reachable, all_isolated, user_crosscheck, system_isolation and

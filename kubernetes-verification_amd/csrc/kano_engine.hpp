@@ -244,6 +244,11 @@ struct kano_ctx {
   std::vector<uint8_t> dead;       // P + inc_A entries
   bool user_edited = false;        // put_rows / set_bit / import: removal cannot rewrite rows
   i64 shadow_total = -1;
+  // the working policy_conflict (kano_conflict_pairs): its own pairs and
+  // total, so an interleaved kano_shadow / kano_shadow_fetch keeps its own
+  // (the scratch -- flags, T, loff, L, tp, poff, tcnt, toff -- is shared)
+  DBuf conflict_out;
+  i64 conflict_total = -1;
   // policy_shadow count-only (kano_verify with shadow_cap < 0): the grouped
   // count (k_shg_*) instead of the pair-by-pair flags
   bool vs_count_only = false;

@@ -2300,7 +2300,7 @@ void kano_destroy(kano_ctx* ctx) {
                   &ctx->gid,    &ctx->cgroup,  &ctx->R,       &ctx->multi,     &ctx->A1,
                   &ctx->A2,     &ctx->own,     &ctx->cross,   &ctx->gmin,      &ctx->gmax,
                   &ctx->flags,  &ctx->T,       &ctx->loff,    &ctx->L,         &ctx->tp,
-                  &ctx->poff,   &ctx->out,     &ctx->scratch_words, &ctx->ident, &ctx->ecls,
+                  &ctx->poff,   &ctx->out,     &ctx->conflict_out, &ctx->scratch_words, &ctx->ident, &ctx->ecls,
                   &ctx->tcnt,   &ctx->toff,    &ctx->sizes,   &ctx->icnt,      &ctx->ioff,
                   &ctx->sysrow, &ctx->wicls,   &ctx->idxd,
                   &ctx->ckey,   &ctx->corder,  &ctx->kcnt,    &ctx->koff,
@@ -2675,6 +2675,7 @@ int build_impl(kano_ctx* ctx, int path, bool rows_now, bool defer_cols = false,
   ctx->rows_dirty = false;
   ctx->cols_valid = false;
   ctx->shadow_total = -1;
+  ctx->conflict_total = -1;
   ctx->sig_armed = 0;   // the syncs below wait on this build's scans only
   ctx->sel_early_cap = -1;
   ctx->shg_prefilled = false;   // (set by this build's shadow_prepare only)
@@ -3236,18 +3237,24 @@ int kano_shadow_fetch(kano_ctx* ctx, int32_t* pairs) {
   return sync(ctx);
 }
 
-int kano_shadow_lists(kano_ctx* ctx, int64_t n_lists, int64_t nbits, int64_t P,
-                      const int64_t* soff, const int32_t* slist, const uint64_t* allow_rows,
-                      int64_t* count) {
+}  // extern "C"
+
+namespace {
+// the tables of explicit per-container policy lists and allow rows
+// (kano_shadow_lists, kano_conflict_lists): every list is its own row class,
+// every pod its own column class; `what` names the entry point in messages
+int lists_setup(kano_ctx* ctx, const char* what, int64_t n_lists, int64_t nbits, int64_t P,
+                const int64_t* soff, const int32_t* slist, const uint64_t* allow_rows) {
   if (!ctx) return -EINVAL;
   if (n_lists < 0 || nbits < 0 || P < 0 || !soff || n_lists >= (int64_t)INT32_MAX / 2)
-    return fail(ctx, -EINVAL, "kano_shadow_lists: bad arguments");
+    return fail(ctx, -EINVAL, std::string(what) + ": bad arguments");
   KCHK(hipSetDevice(ctx->device));
   KTRY(settle(ctx));
   const i64 nnz = soff[n_lists];
   for (i64 e = 0; e < nnz; ++e)
     if (slist[e] < 0 || slist[e] >= P)
-      return fail(ctx, -ERANGE, "kano_shadow_lists: policy index out of range");
+      return fail(ctx, -ERANGE, std::string(what) + ": policy index out of range");
+  ctx->conflict_total = -1;   // (the tables below replace what it was computed from)
   // every list is its own row class; every pod its own column class
   ctx->built = false;
   ctx->lists_mode = true;
@@ -3316,6 +3323,16 @@ int kano_shadow_lists(kano_ctx* ctx, int64_t n_lists, int64_t nbits, int64_t P,
     KLAUNCH();
   }
   ctx->built = true;
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int kano_shadow_lists(kano_ctx* ctx, int64_t n_lists, int64_t nbits, int64_t P,
+                      const int64_t* soff, const int32_t* slist, const uint64_t* allow_rows,
+                      int64_t* count) {
+  KTRY(lists_setup(ctx, "kano_shadow_lists", n_lists, nbits, P, soff, slist, allow_rows));
   return kano_shadow(ctx, count);
 }
 
@@ -3324,6 +3341,165 @@ int kano_conflict(kano_ctx* ctx, int* raises) {
   if (!raises) return fail(ctx, -EINVAL, "kano_conflict: NULL");
   *raises = ctx->max_sel >= 2 ? 1 : 0;
   return 0;
+}
+
+}  // extern "C"
+
+namespace {
+// The working policy_conflict on the shadow layout: k_conflict_test writes
+// the candidate pairs' flags (pairs mode) and T[c]; the scans, the per-pod
+// counts, the compaction and the emission are policy_shadow's.  count_only:
+// no flags, no tile counts.  nl: the class-level pairs (sum of T), total: the
+// per-pod pairs of this context's rows.  kano_verify's state (vs_count_only,
+// the grouped count's tables) is not touched: the next build's fills and
+// shadow_prepare find what they left.
+int conflict_front(kano_ctx* ctx, bool count_only, i64* nl, i64* total) {
+  ShadowPlan sp;
+  sp.U = ctx->rc.U;
+  sp.rl = rows_local(ctx);
+  sp.nf = ctx->nflags;
+  sp.nt = (sp.nf + SH_TILE - 1) / SH_TILE;
+  KTRY(dalloc(ctx, ctx->sizes, sizeof(u64) * SZ_SLOTS));
+  KTRY(dalloc(ctx, ctx->flags, count_only ? 16 : 8 * ((sp.nf + 63) / 64) + 16));
+  KTRY(dalloc(ctx, ctx->T, sizeof(i64) * std::max<i64>(1, sp.U)));
+  KTRY(dalloc(ctx, ctx->loff, sizeof(i64) * (sp.U + 1)));
+  KTRY(dalloc(ctx, ctx->tp, sizeof(i64) * std::max<i64>(1, sp.rl)));
+  KTRY(dalloc(ctx, ctx->poff, sizeof(i64) * (sp.rl + 1)));
+  {
+    FillBatch fb(ctx);
+    if (!count_only) {
+      KTRY(dalloc(ctx, ctx->tcnt, sizeof(i64) * std::max<i64>(1, sp.nt)));
+      KTRY(dalloc(ctx, ctx->toff, sizeof(i64) * (sp.nt + 1)));
+      KTRY(fb.add(ctx->tcnt, sizeof(i64) * sp.nt, 0u));   // accumulated
+    }
+    KTRY(fb.add(ctx->T, sizeof(i64) * sp.U, 0u));
+    KTRY(fb.run());
+  }
+  if (sp.nt > 0) {
+    ShadowArgs a{};
+    a.U = sp.U;
+    a.soffc = P_<i64>(ctx->soffc);
+    a.slist = P_<int32_t>(ctx->slist);
+    a.mcnt = P_<int32_t>(ctx->rc.mcnt);
+    a.pfoff = P_<i64>(ctx->pfoff);
+    a.nca = P_<int32_t>(ctx->nca);
+    a.alcoff = P_<i64>(ctx->alcoff);
+    a.alc = P_<int32_t>(ctx->alc);
+    a.AC = P_<u64>(ctx->AC);
+    a.ldC = ctx->ldC;
+    a.flags = count_only ? nullptr : P_<uint8_t>(ctx->flags);
+    a.T = P_<i64>(ctx->T);
+    // (R as shadow_test_launch chooses it: the shr knob, else by nf)
+    const int R = ctx->shadow_r > 0 ? ctx->shadow_r : (sp.nf >= (i64)1 << 24 ? 8 : 1);
+    const i64 grid = (sp.nf + (i64)TPB * R - 1) / ((i64)TPB * R);
+    i64* tc = count_only ? (i64*)nullptr : P_<i64>(ctx->tcnt);
+    const i64 UA = ctx->cc.U;
+    // (direct launches, no kernel-pointer variable: tests/test_launch_ir.py)
+#define KANO_CFT(RR)                                                                       \
+  hipLaunchKernelGGL((k_conflict_test<1024, RR>), dim3((unsigned)grid), dim3(TPB), 0,      \
+                     ctx->stream, a, sp.nf, tc, UA)
+    if (R == 8) KANO_CFT(8);
+    else if (R == 4) KANO_CFT(4);
+    else if (R == 2) KANO_CFT(2);
+    else KANO_CFT(1);
+#undef KANO_CFT
+    KLAUNCH();
+  }
+  {
+    ScanBatch sb(ctx);
+    if (!count_only) KTRY(sb.add(P_<i64>(ctx->tcnt), sp.nt, P_<i64>(ctx->toff)));
+    KTRY(sb.add(P_<i64>(ctx->T), sp.U, P_<i64>(ctx->loff), SZ_NL));
+    KTRY(sb.run());
+  }
+  {
+    ScanBatch sb(ctx);
+    KTRY(shadow_stage_b(ctx, sp, sb));
+    KTRY(sb.run());
+  }
+  i64 tot[2] = {0, 0};
+  KTRY(read_slots(ctx, SZ_NL, 2, tot));
+  *nl = tot[0];
+  *total = tot[1];
+  return 0;
+}
+
+// the class-level pair lists: L[loff[c] .. loff[c + 1]) of row class c
+int conflict_compact(kano_ctx* ctx, i64 nl) {
+  const i64 U = ctx->rc.U, nf = ctx->nflags;
+  const i64 nt = (nf + SH_TILE - 1) / SH_TILE;
+  KTRY(dalloc(ctx, ctx->L, sizeof(int2) * std::max<i64>(1, nl)));
+  if (nt > 0 && nl > 0) {
+    hipLaunchKernelGGL(k_shadow_compact, dim3((unsigned)nt), dim3(TPB), 0, ctx->stream,
+                       P_<i64>(ctx->soffc), U, P_<int32_t>(ctx->slist), P_<i64>(ctx->pfoff),
+                       P_<uint8_t>(ctx->flags), nf, P_<i64>(ctx->toff), P_<int2>(ctx->L), nl);
+    KLAUNCH();
+  }
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int kano_conflict_pairs(kano_ctx* ctx, int mode, int64_t* count, int64_t* class_pairs) {
+  KTRY(ensure_built(ctx));
+  if (mode != 0 && mode != 1) return fail(ctx, -EINVAL, "kano_conflict_pairs: unknown mode");
+  ctx->conflict_total = -1;
+  i64 nl = 0, total = 0;
+  KTRY(conflict_front(ctx, mode == 1, &nl, &total));
+  if (mode == 0) {
+    const i64 rl = rows_local(ctx);
+    KTRY(dalloc(ctx, ctx->conflict_out, sizeof(int2) * std::max<i64>(1, total)));
+    KTRY(conflict_compact(ctx, nl));
+    if (rl > 0 && total > 0) {
+      hipLaunchKernelGGL(k_shadow_emit, dim3(nblk(rl)), dim3(TPB), 0, ctx->stream,
+                         P_<int32_t>(ctx->rc.cls), ctx->r0, ctx->r1, P_<i64>(ctx->loff),
+                         P_<int2>(ctx->L), P_<i64>(ctx->poff), P_<int2>(ctx->conflict_out), total,
+                         (const i64*)nullptr, nl);
+      KLAUNCH();
+    }
+    ctx->conflict_total = total;
+  }
+  if (count) *count = total;
+  if (class_pairs) *class_pairs = nl;
+  return 0;
+}
+
+int kano_conflict_fetch(kano_ctx* ctx, int32_t* pairs) {
+  KTRY(ensure_built(ctx));
+  if (ctx->conflict_total < 0)
+    return fail(ctx, -EINVAL, "kano_conflict_fetch before kano_conflict_pairs (mode 0)");
+  if (ctx->conflict_total > 0) {
+    if (!pairs) return fail(ctx, -EINVAL, "kano_conflict_fetch: NULL buffer");
+    KCHK(hipMemcpyAsync(pairs, ctx->conflict_out.p, sizeof(int2) * ctx->conflict_total,
+                        hipMemcpyDeviceToHost, ctx->stream));
+  }
+  return sync(ctx);
+}
+
+int kano_conflict_lists(kano_ctx* ctx, int64_t n_lists, int64_t nbits, int64_t P,
+                        const int64_t* soff, const int32_t* slist, const uint64_t* allow_rows,
+                        int mode, int64_t* count) {
+  if (ctx && mode != 0 && mode != 1)
+    return fail(ctx, -EINVAL, "kano_conflict_lists: unknown mode");
+  KTRY(lists_setup(ctx, "kano_conflict_lists", n_lists, nbits, P, soff, slist, allow_rows));
+  return kano_conflict_pairs(ctx, mode, count, nullptr);
+}
+
+int kano_conflict_classes(kano_ctx* ctx, int64_t* off, int32_t* pairs, int32_t* members) {
+  KTRY(ensure_built(ctx));
+  i64 nl = 0, total = 0;
+  KTRY(conflict_front(ctx, false, &nl, &total));
+  KTRY(conflict_compact(ctx, nl));
+  const i64 U = ctx->rc.U;
+  if (off)
+    KCHK(hipMemcpyAsync(off, ctx->loff.p, sizeof(i64) * (U + 1), hipMemcpyDeviceToHost,
+                        ctx->stream));
+  if (pairs && nl > 0)
+    KCHK(hipMemcpyAsync(pairs, ctx->L.p, sizeof(int2) * nl, hipMemcpyDeviceToHost, ctx->stream));
+  if (members && U > 0)
+    KCHK(hipMemcpyAsync(members, ctx->rc.mcnt.p, sizeof(int32_t) * U, hipMemcpyDeviceToHost,
+                        ctx->stream));
+  return sync(ctx);
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 //   column checks              algorithm.py:4-17
 //   user_crosscheck            algorithm.py:27-42
 //   policy_shadow              algorithm.py:58-80
+//   policy_conflict (working)  algorithm.py:83-100 as intended: disjoint allow sets
 #pragma once
 #include "kano_prims.hpp"
 
@@ -2824,6 +2825,172 @@ __global__ __launch_bounds__(TPB) void k_shadow_test1s(ShadowArgs a, i64 nflags,
           if (a.mcnt[c] > 0 && x != y) {
             const int32_t j = a.slist[s0 + x], kk = a.slist[s0 + y];
             f = (j != kk) && subset_of(kk, j, a.nca, a.alcoff, a.alc, a.AC, a.ldC);
+          }
+        }
+      }
+      // the flags as bits, one ballot word per wave (the wave's 64 pairs are
+      // consecutive: b0 is a multiple of 256); null: count only (T[c])
+      {
+        const u64 bal = __ballot(f != 0);
+        const i64 w0 = b0 + (i64)(threadIdx.x & ~63);
+        if (a.flags && (threadIdx.x & 63) == 0 && w0 < nflags)
+          reinterpret_cast<u64*>(a.flags)[w0 >> 6] = bal;
+      }
+      const i64 cw = __shfl(c, 0, 64);
+      if (__all(c == cw || c < 0)) {
+        const int rr = wave_sum(f);
+        if ((threadIdx.x & 63) == 0 && rr && cw >= 0)
+          atomicAdd(reinterpret_cast<unsigned long long*>(&a.T[cw]), (unsigned long long)rr);
+      } else if (f) {
+        atomicAdd(reinterpret_cast<unsigned long long*>(&a.T[c]), 1ull);
+      }
+      const i64 tot = block_sum((i64)f, sm);
+      if (threadIdx.x == 0 && tot && tile_cnt)   // (null: count only)
+        atomicAdd(reinterpret_cast<unsigned long long*>(&tile_cnt[tile]), (unsigned long long)tot);
+    }
+    if ((i64)gridDim.x >= nvb) break;           // one virtual block per block (uniform)
+    __syncthreads();                             // LDS reused by the next virtual block
+  }
+}
+
+// ===========================================================================
+// The working policy_conflict (the reference's loop,
+// algorithm.py:83-100, raises before it answers).  Pair (a, b) of S(c)
+// positions, S[a] != S[b]:  flag = allow_{S[a]} and allow_{S[b]} share no pod.
+// Tested on column classes: they partition the pods and every class holds at
+// least one pod, so two policies share a pod exactly when they share an
+// allowed class (a shared class has a member that both allow; a shared pod
+// lies in one class, which both then allow).  In lists mode every pod is its
+// own class.  Same candidate layout, flag words, T[c] and tile counts as
+// k_shadow_test1s, so k_shadow_compact / _podcount / _emit run on the result.
+//
+// The shorter allowed-class list is walked against the other policy's AC
+// row.  No load at all: an empty allow set is disjoint from everything;
+// nca[j] + nca[k] > UA (the column classes) must overlap (pigeonhole).
+// Unlike the subset test, whose typical pair fails on the first class, the
+// typical pair of a sparse cluster IS a conflict and walks its whole list:
+// CF_U independent loads per round.
+// ===========================================================================
+constexpr int CF_U = 8;
+
+__device__ __forceinline__ bool disjoint_walk(const int32_t* __restrict__ L, int32_t cnt,
+                                              const u64* __restrict__ row, int32_t x0) {
+  bool dis = !((row[x0 >> 6] >> (x0 & 63)) & 1ull);      // x0 = L[0]
+  for (int32_t e = 1; dis && e < cnt; e += CF_U) {
+    int32_t xs[CF_U];
+#pragma unroll
+    for (int u = 0; u < CF_U; ++u) xs[u] = e + u < cnt ? L[e + u] : x0;
+    u64 ws[CF_U];
+#pragma unroll
+    for (int u = 0; u < CF_U; ++u) ws[u] = row[xs[u] >> 6];
+#pragma unroll
+    for (int u = 0; u < CF_U; ++u) dis = dis && !((ws[u] >> (xs[u] & 63)) & 1ull);
+  }
+  return dis;
+}
+
+// the global form (blocks whose class range or S(c) segment is not staged)
+__device__ __forceinline__ bool disjoint_of(int32_t j, int32_t k, const int32_t* nca,
+                                            const i64* alcoff, const int32_t* alc, const u64* AC,
+                                            i64 ldC, i64 UA) {
+  const int32_t cj = nca[j], ck = nca[k];
+  if (cj == 0 || ck == 0) return true;
+  if ((i64)cj + ck > UA) return false;
+  const int32_t s = ck <= cj ? k : j, o = ck <= cj ? j : k;   // short list, other row
+  const int32_t* L = alc + alcoff[s];
+  return disjoint_walk(L, min(cj, ck), AC + (i64)o * ldC, L[0]);
+}
+
+template <int CFS_SEG, int R>
+__global__ __launch_bounds__(TPB) void k_conflict_test(ShadowArgs a, i64 nflags,
+                                                      i64* __restrict__ tile_cnt, i64 UA) {
+  __shared__ i64 sm[4];
+  __shared__ i64 rng[2];
+  __shared__ i64 s_pf[SHS_CLS];
+  __shared__ i64 s_so[SHS_CLS];
+  __shared__ int32_t s_mc[SHS_CLS];
+  __shared__ i64 s_ao[CFS_SEG];
+  __shared__ int32_t s_pol[CFS_SEG];
+  __shared__ int32_t s_nca[CFS_SEG];
+  __shared__ int32_t s_x0[CFS_SEG];
+  static_assert(SH_TILE % (TPB * R) == 0, "a block's pairs stay inside one tile");
+  constexpr i64 PB = (i64)TPB * R;               // pairs per virtual block
+  const i64 nvb = (nflags + PB - 1) / PB;
+  for (i64 vb = blockIdx.x; vb < nvb; vb += gridDim.x) {
+    const i64 B0 = vb * PB;
+    if (B0 >= nflags) break;                     // block-uniform (B0 rises with vb)
+    const i64 B1 = min(B0 + PB, nflags) - 1;
+    if ((threadIdx.x >> 6) < 2) {
+      const int wv = threadIdx.x >> 6;
+      const i64 cr = wave_class_of(a.pfoff, 0, a.U - 1, wv == 0 ? B0 : B1);
+      if ((threadIdx.x & 63) == 0) rng[wv] = cr;
+    }
+    __syncthreads();
+    const i64 c0 = rng[0], c1 = rng[1];
+    const i64 ncls = c1 - c0 + 1;
+    const bool staged_cls = ncls + 1 <= SHS_CLS;
+    i64 seg0 = 0, nseg = CFS_SEG + 1;
+    if (staged_cls) {
+      for (i64 k = threadIdx.x; k <= ncls; k += TPB) {
+        s_pf[k] = a.pfoff[c0 + k];
+        s_so[k] = a.soffc[c0 + k];
+        if (k < ncls) s_mc[k] = a.mcnt[c0 + k];
+      }
+      __syncthreads();
+      seg0 = s_so[0];
+      nseg = s_so[ncls] - seg0;
+    }
+    const bool staged = staged_cls && nseg <= CFS_SEG;   // block-uniform
+    if (staged) {
+      for (i64 e = threadIdx.x; e < nseg; e += TPB) {
+        const int32_t p = a.slist[seg0 + e];
+        const int32_t cnt = a.nca[p];
+        const i64 ao = a.alcoff[p];
+        s_pol[e] = p;
+        s_nca[e] = cnt;
+        s_ao[e] = ao;
+        s_x0[e] = cnt > 0 ? a.alc[ao] : 0;
+      }
+      __syncthreads();
+    }
+    for (int r = 0; r < R; ++r) {
+      const i64 b0 = B0 + (i64)r * TPB;
+      if (b0 >= nflags) break;                   // block-uniform
+      const i64 tile = b0 / SH_TILE;
+      const i64 t = b0 + threadIdx.x;
+      int f = 0;
+      i64 c = -1;
+      if (t < nflags) {
+        if (staged) {
+          i64 lo = 0, hi = ncls - 1;             // last class with pfoff <= t
+          while (lo < hi) {
+            const i64 mid = (lo + hi + 1) >> 1;
+            if (s_pf[mid] <= t) lo = mid; else hi = mid - 1;
+          }
+          c = c0 + lo;
+          const i64 e0 = s_so[lo] - seg0, s = s_so[lo + 1] - s_so[lo], q = t - s_pf[lo];
+          const i64 x = q / s, y = q - x * s;
+          if (s_mc[lo] > 0 && x != y) {
+            const int32_t j = s_pol[e0 + x], kk = s_pol[e0 + y];
+            const int32_t cj = s_nca[e0 + x], ck = s_nca[e0 + y];
+            if (j != kk) {
+              if (cj == 0 || ck == 0) {
+                f = 1;
+              } else if ((i64)cj + ck <= UA) {
+                const bool ys = ck <= cj;        // y's list is the short one
+                const i64 es = e0 + (ys ? y : x);
+                const u64* row = a.AC + (i64)(ys ? j : kk) * a.ldC;
+                f = disjoint_walk(a.alc + s_ao[es], ys ? ck : cj, row, s_x0[es]);
+              }
+            }
+          }
+        } else {
+          c = class_of_pair(a.pfoff, c0, c1, t);
+          const i64 s0 = a.soffc[c], s = a.soffc[c + 1] - s0, q = t - a.pfoff[c];
+          const i64 x = q / s, y = q - x * s;
+          if (a.mcnt[c] > 0 && x != y) {
+            const int32_t j = a.slist[s0 + x], kk = a.slist[s0 + y];
+            f = (j != kk) && disjoint_of(j, kk, a.nca, a.alcoff, a.alc, a.AC, a.ldC, UA);
           }
         }
       }

@@ -569,6 +569,40 @@ class DeviceBuild:
         self._chk(self.lib.kano_conflict(self.ctx, byref(v)), "kano_conflict")
         return bool(v.value)
 
+    # -- the working policy_conflict (kano_conflict_pairs) ---------------
+    def _conflict_run(self, mode: int) -> Tuple[int, int]:
+        cnt, ncls = c_int64(), c_int64()
+        self._chk(self.lib.kano_conflict_pairs(self.ctx, int(mode), byref(cnt), byref(ncls)),
+                  "kano_conflict_pairs")
+        return int(cnt.value), int(ncls.value)
+
+    def conflict_count(self) -> int:
+        """Pairs (j, k) of policies selecting a common pod of this context's
+        rows with disjoint allow sets, counted only (no pairs on the device)."""
+        return self._conflict_run(1)[0]
+
+    def conflict_fetch(self, count: int, out: Optional[np.ndarray] = None) -> np.ndarray:
+        if out is None:
+            out = np.zeros((count, 2), dtype=np.int32)
+        self._chk(self.lib.kano_conflict_fetch(self.ctx, _ptr(out)), "kano_conflict_fetch")
+        return out
+
+    def conflict(self) -> np.ndarray:
+        """The pairs as a (count, 2) int32 array, in container order."""
+        return self.conflict_fetch(self._conflict_run(0)[0])
+
+    def conflict_classes(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Class level: (off, pairs, members) -- row class c's conflicting
+        pairs are pairs[off[c]:off[c + 1]], shared by its members[c] pods."""
+        ncls = self._conflict_run(1)[1]
+        U = self.info()["U"]
+        off = np.zeros(U + 1, dtype=np.int64)
+        pairs = np.zeros((ncls, 2), dtype=np.int32)
+        members = np.zeros(U, dtype=np.int32)
+        self._chk(self.lib.kano_conflict_classes(self.ctx, _ptr(off), _ptr(pairs), _ptr(members)),
+                  "kano_conflict_classes")
+        return off, pairs, members
+
     def rows_timing(self, reset: bool = False) -> dict:
         """k_rows launch times (HIP events) since the last reset: sum, count,
         min, max (ms); waits for the context's work."""
@@ -648,3 +682,29 @@ def shadow_from_lists(n_lists: int, nbits: int, soff: np.ndarray, slist: np.ndar
     b._chk(lib.kano_shadow_fetch(b.ctx, _ptr(out)), "kano_shadow_fetch")
     b.close()
     return out
+
+
+def conflict_from_lists(n_lists: int, nbits: int, soff: np.ndarray, slist: np.ndarray,
+                        allow_words: np.ndarray, device: int = 0,
+                        count_only: bool = False):
+    """The working policy_conflict over explicit per-container policy lists
+    and allow sets (kano_conflict_lists): the (count, 2) pairs, or with
+    ``count_only`` their number."""
+    lib = nat.load()
+    b = DeviceBuild(None, device=device)
+    try:
+        P = allow_words.shape[0]
+        soff = np.ascontiguousarray(soff, dtype=np.int64)
+        slist = np.ascontiguousarray(slist, dtype=np.int32)
+        aw = np.ascontiguousarray(allow_words, dtype=np.uint64)
+        cnt = c_int64()
+        b._chk(lib.kano_conflict_lists(b.ctx, int(n_lists), int(nbits), int(P), _ptr(soff),
+                                       _ptr(slist), _ptr(aw), 1 if count_only else 0,
+                                       byref(cnt)), "kano_conflict_lists")
+        if count_only:
+            return int(cnt.value)
+        out = np.zeros((int(cnt.value), 2), dtype=np.int32)
+        b._chk(lib.kano_conflict_fetch(b.ctx, _ptr(out)), "kano_conflict_fetch")
+        return out
+    finally:
+        b.close()

@@ -141,10 +141,19 @@ def policy_shadow_pairs(matrix: ReachabilityMatrix, policies: List[Policy],
     """policy_shadow as an (T, 2) int32 array (compact form, same order)."""
     if _fast_path(matrix, policies, containers):
         return _engine(matrix).shadow()
-    # general form: explicit per-container lists (accumulated builds, edited
-    # lists) and each policy's current working_allow_set
     from ._engine import shadow_from_lists
+    n_lists, nbits, soff, flat, aw = _explicit_lists(policies, containers)
+    return shadow_from_lists(n_lists, nbits, soff, flat, aw, device=_engine(matrix).device)
+
+
+def _explicit_lists(policies: List[Policy], containers: List[Container], dedup: bool = False):
+    """The general form's inputs: explicit per-container lists (accumulated
+    builds, edited lists) and each policy's current working_allow_set, as
+    (n_lists, nbits, soff, flat int32, allow words).  ``dedup``: every list
+    as its set of ids."""
     lists = [list(c.select_policies) for c in containers]
+    if dedup:
+        lists = [sorted(set(l)) for l in lists]
     soff = np.zeros(len(lists) + 1, dtype=np.int64)
     np.cumsum([len(l) for l in lists], out=soff[1:])
     flat = np.fromiter((x for l in lists for x in l), dtype=np.int64, count=int(soff[-1]))
@@ -168,8 +177,7 @@ def policy_shadow_pairs(matrix: ReachabilityMatrix, policies: List[Policy],
         s = policies[p].working_allow_set
         b = s if isinstance(s, BitArray) else BitArray(s)
         aw[p] = b.words()[:W]
-    return shadow_from_lists(len(lists), nbits, soff, flat.astype(np.int32), aw,
-                             device=_engine(matrix).device)
+    return len(lists), nbits, soff, flat.astype(np.int32), aw
 
 
 def policy_shadow(matrix: ReachabilityMatrix, policies: List[Policy],
@@ -192,6 +200,74 @@ def policy_conflict(matrix: ReachabilityMatrix, policies: List[Policy],
     if raises:
         raise AttributeError("'int' object has no attribute 'working_allow_set'")
     return []
+
+
+# ---------------------------------------------------------------------------
+# The working policy_conflict.  policy_conflict above reproduces the
+# reference's AttributeError; these answer the question its loop was written
+# for: which policies selecting the same container have
+# allow sets with no container in common?  Same iteration as policy_shadow:
+# containers ascending, j then k in select_policies order, j == k skipped by
+# value, one entry per container (duplicates kept, quirk Q4).  The relation is
+# symmetric, so (j, k) and (k, j) both appear; an empty allow set conflicts
+# with every other policy.
+
+def policy_conflict_pairs(matrix: ReachabilityMatrix, policies: List[Policy],
+                          containers: List[Container]) -> np.ndarray:
+    """The conflicting pairs as an (T, 2) int32 array."""
+    if _fast_path(matrix, policies, containers):
+        return _engine(matrix).conflict()
+    from ._engine import conflict_from_lists
+    n_lists, nbits, soff, flat, aw = _explicit_lists(policies, containers)
+    return conflict_from_lists(n_lists, nbits, soff, flat, aw, device=_engine(matrix).device)
+
+
+def policy_conflicts(matrix: ReachabilityMatrix, policies: List[Policy],
+                     containers: List[Container]) -> List[Tuple[int, int]]:
+    """Pairs (j, k) of policies selecting a common container whose allow sets
+    are disjoint, one entry per container, in container order."""
+    return _pairs_to_list(policy_conflict_pairs(matrix, policies, containers), len(policies))
+
+
+def policy_conflict_count(matrix: ReachabilityMatrix, policies: List[Policy],
+                          containers: List[Container]) -> int:
+    """len(policy_conflicts(...)) without the pairs (sparse clusters make
+    nearly every candidate pair a conflict)."""
+    if _fast_path(matrix, policies, containers):
+        return _engine(matrix).conflict_count()
+    from ._engine import conflict_from_lists
+    n_lists, nbits, soff, flat, aw = _explicit_lists(policies, containers)
+    return conflict_from_lists(n_lists, nbits, soff, flat, aw, device=_engine(matrix).device,
+                               count_only=True)
+
+
+def policy_conflict_summary(matrix: ReachabilityMatrix, policies: List[Policy],
+                            containers: List[Container]) -> List[Tuple[int, int, int]]:
+    """The distinct conflicting pairs j < k, ascending, each with the number
+    of containers that both policies select: [(j, k, containers), ...].
+    Aggregated on the host from the class-level lists (the per-container pair
+    list of a large sparse cluster runs to ~1e8 entries)."""
+    P = len(policies)
+    if _fast_path(matrix, policies, containers):
+        eng = _engine(matrix)
+        if hasattr(eng, "conflict_classes"):
+            off, pairs, members = eng.conflict_classes()
+            weight = np.repeat(members.astype(np.int64), np.diff(off))
+        else:                    # (a row-sharded group: its members' pair lists)
+            pairs = eng.conflict()
+            weight = np.ones(pairs.shape[0], dtype=np.int64)
+    else:
+        # (every list as a set: a repeated id would count its container twice)
+        from ._engine import conflict_from_lists
+        n_lists, nbits, soff, flat, aw = _explicit_lists(policies, containers, dedup=True)
+        pairs = conflict_from_lists(n_lists, nbits, soff, flat, aw,
+                                    device=_engine(matrix).device)
+        weight = np.ones(pairs.shape[0], dtype=np.int64)
+    keep = pairs[:, 0] < pairs[:, 1]
+    key = pairs[keep, 0].astype(np.int64) * max(P, 1) + pairs[keep, 1]
+    uniq, inv = np.unique(key, return_inverse=True)
+    tot = np.bincount(inv, weights=weight[keep], minlength=uniq.size).astype(np.int64)
+    return [(int(k // max(P, 1)), int(k % max(P, 1)), int(t)) for k, t in zip(uniq, tot)]
 
 
 # ---------------------------------------------------------------------------

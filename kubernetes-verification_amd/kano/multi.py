@@ -307,6 +307,15 @@ class MultiBuild:
     def conflict_raises(self) -> bool:
         return any(m.conflict_raises() for m in self.members)
 
+    def conflict(self) -> np.ndarray:
+        """The working policy_conflict's pairs: each member's (its
+        containers), rank order."""
+        parts = [m.conflict() for m in self.members]
+        return np.concatenate(parts).reshape(-1, 2) if parts else np.zeros((0, 2), np.int32)
+
+    def conflict_count(self) -> int:
+        return sum(m.conflict_count() for m in self.members)
+
     # -- matrix access: owners --------------------------------------------
     def rows(self, r0: int, nrows: int, out: Optional[np.ndarray] = None) -> np.ndarray:
         if out is None:
