@@ -190,6 +190,33 @@ int kano_conflict_lists(kano_ctx* ctx, int64_t n_lists, int64_t nbits, int64_t P
 int kano_conflict_classes(kano_ctx* ctx, int64_t* off /* U+1 */, int32_t* pairs,
                           int32_t* members /* U */);
 
+/* policy_impact / policy_redundant: what removing one policy changes.  With
+ * cover(i,j) = #{p : i in select_p, j in allow_p} over the working sets,
+ *   impact[p] = #{(i,j) : i in select_p, j in allow_p, cover(i,j) == 1},
+ * the pod pairs that lose reachability when p alone is removed (the bits in
+ * which the matrix differs after removing p), counted over this context's
+ * rows r0..r1: the impacts of row shards add up, their flags OR.  p is
+ * redundant iff impact[p] == 0 (an empty select or allow set; a policy
+ * covered by the union of others; each of two identical policies).
+ * mode 0: impact[P] (required), essential[P] (nullable; 1 = not redundant)
+ * and *n_redundant (nullable).  mode 1: the flags and the count only, impact
+ * may be NULL.  Any other mode returns -EINVAL.  Exact integers.  The device
+ * buffers are the call's own: kano_shadow_fetch / kano_conflict_fetch after
+ * it return their own results, a call between pipelined kano_verify steps
+ * leaves the next step unchanged, and a failed allocation returns -ENOMEM
+ * and leaves the context usable. */
+int kano_policy_impact(kano_ctx* ctx, int mode, int64_t* impact /* P, NULL in mode 1 */,
+                       uint8_t* essential /* P, nullable */, int64_t* n_redundant);
+/* The same over explicit inputs (the arguments of kano_shadow_lists): list c
+ * is one container's selecting policies, allow_rows[p] the pods p allows.
+ * Unlike the shadow and conflict entry points this one needs the ids within
+ * one list distinct: a repeated id returns -EINVAL, an id outside [0, P)
+ * -ERANGE.  The context holds no matrix afterwards. */
+int kano_policy_impact_lists(kano_ctx* ctx, int64_t n_lists, int64_t nbits, int64_t P,
+                             const int64_t* soff, const int32_t* slist,
+                             const uint64_t* allow_rows, int mode,
+                             int64_t* impact, uint8_t* essential, int64_t* n_redundant);
+
 /* The whole verification pass in one call (the sequence kano_py's
  * sample/example.py and tests/test_basic.py run: build_matrix, then
  * all_reachable, all_isolated, user_crosscheck, system_isolation and
@@ -309,9 +336,10 @@ int kano_set_groups(kano_ctx* ctx, const int32_t* gid, int32_t ngroups);
 
 /* Timing of the last kano_build / kano_shadow stages on the context stream
  * (HIP events), milliseconds: [classes, allow, select + plan, rows stage,
- * shadow, build total, k_rows kernel alone, 0].  Slots 0-5 are recorded only
- * when the context was created with KANO_TUNE=timing=1 (each event costs
- * host time on the launch path); slot 6 always. */
+ * shadow, build total, k_rows kernel alone, policy_impact].  Slots 0-5 are
+ * recorded only when the context was created with KANO_TUNE=timing=1 (each
+ * event costs host time on the launch path); slot 6 always; slot 7, the last
+ * kano_policy_impact's fill and kernel without the copy, also under timing=1. */
 int kano_stage_times(kano_ctx* ctx, float* ms /* 8 */);
 
 /* k_rows launch times (the matrix write of model.py:158-160; HIP events on

@@ -163,6 +163,7 @@ struct kano_ctx {
   int rows_ch = ROWS_CH;     // rch=: member rows per k_rows work item
   int rows_cww = MAX_CWW_KNOB;   // cww: k_rows column chunk (words); the chunking wide matrices
                              // (n > 524k) take, forced at small n
+  int impact_form = 0;       // impf=1/2: policy_impact's list / row form forced (0: by density)
   int shadow_r = 0;          // shr=1/2/4/8: k_shadow_test1s's 256-pair rounds per block (0: auto)
   int shg_sub_lds = 1;       // shgsub=0: forces k_shg_sub's word-by-word row compare (the
                              // form rows wider than 64 KB of LDS take)
@@ -249,6 +250,10 @@ struct kano_ctx {
   // (the scratch -- flags, T, loff, L, tp, poff, tcnt, toff -- is shared)
   DBuf conflict_out;
   i64 conflict_total = -1;
+  // policy_impact / policy_redundant (kano_policy_impact): the per-policy
+  // sums and essential flags, no other buffer written
+  DBuf impact_out, impact_ess;
+  float impact_ms = 0.f;      // timing=1: the last call's device time (fill + kernel)
   // policy_shadow count-only (kano_verify with shadow_cap < 0): the grouped
   // count (k_shg_*) instead of the pair-by-pair flags
   bool vs_count_only = false;

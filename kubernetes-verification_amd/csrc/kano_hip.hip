@@ -2126,6 +2126,7 @@ int kano_create(int device, kano_ctx** out) {
         if (k == "pathlds") ctx->path_lds = v;
         if (k == "pathtn" && (v == 2 || v == 4)) ctx->path_tn = v;
         if (k == "shgsub") ctx->shg_sub_lds = v;
+        if (k == "impf" && v >= 0 && v <= 2) ctx->impact_form = v;
         if (k == "shr" && (v == 1 || v == 2 || v == 4 || v == 8)) ctx->shadow_r = v;
         if (k == "rcu" && v >= 0 && v <= 28 && (v < 4 || v % 4 == 0)) ctx->rows_cu_off = v;
         if (k == "rcubytes" && v >= 0) ctx->rows_cu_bytes = (i64)v << 30;
@@ -2301,6 +2302,7 @@ void kano_destroy(kano_ctx* ctx) {
                   &ctx->A2,     &ctx->own,     &ctx->cross,   &ctx->gmin,      &ctx->gmax,
                   &ctx->flags,  &ctx->T,       &ctx->loff,    &ctx->L,         &ctx->tp,
                   &ctx->poff,   &ctx->out,     &ctx->conflict_out, &ctx->scratch_words, &ctx->ident, &ctx->ecls,
+                  &ctx->impact_out, &ctx->impact_ess,
                   &ctx->tcnt,   &ctx->toff,    &ctx->sizes,   &ctx->icnt,      &ctx->ioff,
                   &ctx->sysrow, &ctx->wicls,   &ctx->idxd,
                   &ctx->ckey,   &ctx->corder,  &ctx->kcnt,    &ctx->koff,
@@ -3505,6 +3507,154 @@ int kano_conflict_classes(kano_ctx* ctx, int64_t* off, int32_t* pairs, int32_t* 
 }  // extern "C"
 
 namespace {
+// policy_impact on the resident class tables (k_impact_list / k_impact_rows):
+// mode 0 the impacts (the flags follow from them: every column class has a
+// member, so a unique cell weighs at least 1), mode 1 the flags alone.  Only
+// impact_out / impact_ess are written: policy_shadow's and policy_conflict's
+// results and kano_verify's state stay as they are.
+int impact_run(kano_ctx* ctx, int mode, int64_t* impact, uint8_t* essential,
+               int64_t* n_redundant) {
+  const i64 P = ctx->P, U = ctx->rc.U, UA = ctx->cc.U;
+  if (mode == 0 && !impact && P > 0) return fail(ctx, -EINVAL, "kano_policy_impact: NULL impact");
+  DBuf& res = mode == 0 ? ctx->impact_out : ctx->impact_ess;
+  const size_t bytes = (mode == 0 ? sizeof(i64) : sizeof(uint8_t)) * (size_t)P;
+  KTRY(dalloc(ctx, res, bytes));
+  // timing=1: the call's device time (the fill and the kernel, no copy) for
+  // kano_stage_times, slot 7
+  hipEvent_t tev[2] = {nullptr, nullptr};
+  if (ctx->stage_timing) {
+    KCHK(hipEventCreate(&tev[0]));
+    KCHK(hipEventCreate(&tev[1]));
+    KCHK(hipEventRecord(tev[0], ctx->stream));
+  }
+  if (P > 0) KCHK(hipMemsetAsync(res.p, 0, bytes, ctx->stream));
+  if (P > 0 && U > 0 && UA > 0) {
+    ImpactArgs a{};
+    a.soffc = P_<i64>(ctx->soffc);
+    a.slist = P_<int32_t>(ctx->slist);
+    a.mcnt = P_<int32_t>(ctx->rc.mcnt);
+    a.nca = P_<int32_t>(ctx->nca);
+    a.alcoff = P_<i64>(ctx->alcoff);
+    a.alc = P_<int32_t>(ctx->alc);
+    a.AC = P_<u64>(ctx->AC);
+    a.ldC = ctx->ldC;
+    a.UA = UA;
+    a.cw = ctx->lists_mode ? nullptr : P_<int32_t>(ctx->cc.mcnt);   // lists: every pod a class
+    a.impact = P_<i64>(ctx->impact_out);
+    a.ess = P_<uint8_t>(ctx->impact_ess);
+    // The form, from the tables' mean shape (s = policies per row class, nca =
+    // allowed classes per policy), in rounds a block makes over its class:
+    //   rows  ceil(UAW / IMP_RW) blocks x ceil(s / TPB) rounds (a lane per policy)
+    //   list  tiles blocks x ceil(s / WPB) x ceil(nca / 64) rounds (a wave per policy)
+    // The list form wins where a few policies select a class and the bit rows
+    // are long (C3: 85 to 1), the row form where hundreds select it or the rows
+    // are a few words (C4: 1 to 125); DESIGN.md has the measurements.
+    const i64 UAW = (UA + 63) / 64;
+    const i64 row_tiles = (UAW + IMP_RW - 1) / IMP_RW;
+    // one LDS tile per block; few row classes: narrower tiles, so that the
+    // grid still fills the device (the lists are walked once per tile)
+    i64 tb = IMP_TB;
+    while (tb > IMP_TB_MIN && U * ((UA + tb - 1) / tb) < IMP_GRID_MIN && tb / 2 >= (UA + 15) / 16)
+      tb /= 2;
+    const i64 list_tiles = (UA + tb - 1) / tb;
+    const i64 sbar = (ctx->nnz_sel + U - 1) / U, ncabar = (ctx->nnz_alc + P - 1) / P;
+    const i64 row_rounds = row_tiles * ((sbar + TPB - 1) / TPB);
+    const i64 list_rounds =
+        list_tiles * ((sbar + WPB - 1) / WPB) * std::max<i64>(1, (ncabar + 63) / 64);
+    bool rows = row_rounds <= list_rounds;
+    if (ctx->impact_form) rows = ctx->impact_form == 2;
+    if (row_tiles > 65535) rows = false;
+    if (rows) {
+      const dim3 grid((unsigned)U, (unsigned)row_tiles);
+      // (direct launches, no kernel-pointer variable: tests/test_launch_ir.py)
+      if (mode == 0) hipLaunchKernelGGL((k_impact_rows<true>), grid, dim3(TPB), 0, ctx->stream, a);
+      else hipLaunchKernelGGL((k_impact_rows<false>), grid, dim3(TPB), 0, ctx->stream, a);
+    } else {
+      const dim3 grid((unsigned)U, (unsigned)list_tiles);
+      if (mode == 0)
+        hipLaunchKernelGGL((k_impact_list<true>), grid, dim3(TPB), 0, ctx->stream, a, tb);
+      else
+        hipLaunchKernelGGL((k_impact_list<false>), grid, dim3(TPB), 0, ctx->stream, a, tb);
+    }
+    KLAUNCH();
+  }
+  if (tev[0]) {
+    KCHK(hipEventRecord(tev[1], ctx->stream));
+    KCHK(hipEventSynchronize(tev[1]));
+    (void)hipEventElapsedTime(&ctx->impact_ms, tev[0], tev[1]);
+    (void)hipEventDestroy(tev[0]);
+    (void)hipEventDestroy(tev[1]);
+  }
+  i64 nred = 0;
+  if (mode == 0) {
+    if (P > 0)
+      KCHK(hipMemcpyAsync(impact, res.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    KTRY(sync(ctx));
+    for (i64 p = 0; p < P; ++p) {
+      nred += impact[p] == 0;
+      if (essential) essential[p] = impact[p] != 0;
+    }
+  } else {
+    std::vector<uint8_t> own;
+    if (!essential) {
+      own.resize((size_t)std::max<i64>(1, P));
+      essential = own.data();
+    }
+    if (P > 0)
+      KCHK(hipMemcpyAsync(essential, res.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    KTRY(sync(ctx));
+    for (i64 p = 0; p < P; ++p) nred += essential[p] == 0;
+  }
+  if (n_redundant) *n_redundant = nred;
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int kano_policy_impact(kano_ctx* ctx, int mode, int64_t* impact, uint8_t* essential,
+                       int64_t* n_redundant) {
+  KTRY(ensure_built(ctx));
+  if (mode != 0 && mode != 1) return fail(ctx, -EINVAL, "kano_policy_impact: unknown mode");
+  // (the class tables are the build's: added or removed policies are not in them)
+  if (ctx->inc_A > 0 || std::find(ctx->dead.begin(), ctx->dead.end(), 1) != ctx->dead.end())
+    return fail(ctx, -EINVAL,
+                "kano_policy_impact: the build's tables no longer match the matrix (policies "
+                "added or removed); use kano_policy_impact_lists");
+  return impact_run(ctx, mode, impact, essential, n_redundant);
+}
+
+int kano_policy_impact_lists(kano_ctx* ctx, int64_t n_lists, int64_t nbits, int64_t P,
+                             const int64_t* soff, const int32_t* slist,
+                             const uint64_t* allow_rows, int mode, int64_t* impact,
+                             uint8_t* essential, int64_t* n_redundant) {
+  if (!ctx) return -EINVAL;
+  if (mode != 0 && mode != 1)
+    return fail(ctx, -EINVAL, "kano_policy_impact_lists: unknown mode");
+  if (n_lists < 0 || nbits < 0 || P < 0 || !soff)
+    return fail(ctx, -EINVAL, "kano_policy_impact_lists: bad arguments");
+  // the saturating count needs the ids of one list distinct (a repeated id
+  // would count its own cells twice): one stamp per policy, O(nnz)
+  {
+    std::vector<i64> stamp((size_t)P, -1);
+    for (i64 c = 0; c < n_lists; ++c)
+      for (i64 e = soff[c]; e < soff[c + 1]; ++e) {
+        const int32_t p = slist[e];
+        if (p < 0 || p >= P)
+          return fail(ctx, -ERANGE, "kano_policy_impact_lists: policy index out of range");
+        if (stamp[p] == c)
+          return fail(ctx, -EINVAL, "kano_policy_impact_lists: policy " + std::to_string(p) +
+                                        " twice in list " + std::to_string(c));
+        stamp[p] = c;
+      }
+  }
+  KTRY(lists_setup(ctx, "kano_policy_impact_lists", n_lists, nbits, P, soff, slist, allow_rows));
+  return impact_run(ctx, mode, impact, essential, n_redundant);
+}
+
+}  // extern "C"
+
+namespace {
 // kano_verify in two halves.  verify_front: the build and every check up to
 // the column words (k_verify_cols; with words_dev also this shard's
 // [OR | cross | NAND] words for the ranks' gather).  verify_back: (combine
@@ -4320,6 +4470,7 @@ int kano_stage_times(kano_ctx* ctx, float* ms) {
   }
   if (ctx->stage_timing && ctx->shadow_total >= 0)
     (void)hipEventElapsedTime(&ms[4], ctx->ev[5], ctx->ev[6]);
+  ms[7] = ctx->impact_ms;   // (the last kano_policy_impact under timing=1)
   return 0;
 }
 

@@ -3019,6 +3019,192 @@ __global__ __launch_bounds__(TPB) void k_conflict_test(ShadowArgs a, i64 nflags,
   }
 }
 
+// ===========================================================================
+// policy_impact / policy_redundant: what removing one policy changes.
+//   cover(i, j) = #{p : i in sel_p, j in allow_p}
+//   impact[p]   = #{(i, j) : i in sel_p, j in allow_p, cover(i, j) == 1}
+// p is redundant when impact[p] == 0.  On classes: the pods of a row class c
+// share S(c), the pods of a column class share the policies allowing them, and
+// every column class has a member, so with cover_c(x) = #{p in S(c) : x in
+// alc(p)}
+//   impact[p] = sum_{c : p in S(c)} mcnt[c] * sum_{x in alc(p), cover_c(x) == 1} cw[x]
+// (cw = the column classes' member counts; null in lists mode, every pod its
+// own class).  Row classes without a member in this shard are skipped.
+//
+// Per row class: pass 1 finds the column classes allowed at least once and at
+// least twice (two bit planes: the count saturates at 2, it never wraps),
+// pass 2 gives every policy of S(c) its cells in once & ~twice.  IMPACT: the
+// weighted sum into impact[p] (64-bit atomic); else only ess[p] = 1.  The ids
+// of one S(c) are distinct (the build lists a policy once per class; the
+// lists entry point checks it).
+//
+// Two forms, chosen per call by the host from the tables' mean shape:
+//   k_impact_list  walks the allowed-class lists; the planes live in LDS, one
+//                  block per (row class, range of tb column classes)
+//   k_impact_rows  walks the AC bit rows, a lane per policy of S(c); the
+//                  planes stay in registers, one block per (row class,
+//                  IMP_RW words of column classes)
+// Both grids split a class's work by column range (columns are independent),
+// so a class with hundreds of policies does not sit in one block.
+// ===========================================================================
+struct ImpactArgs {
+  const i64* soffc;
+  const int32_t* slist;
+  const int32_t* mcnt;
+  const int32_t* nca;
+  const i64* alcoff;
+  const int32_t* alc;
+  const u64* AC;
+  i64 ldC;
+  i64 UA;                // column classes
+  const int32_t* cw;     // members per column class (null: 1)
+  i64* impact;           // IMPACT
+  uint8_t* ess;          // !IMPACT
+};
+
+constexpr int IMP_TB = 32768;   // column classes per LDS tile: two planes of 4 KB
+constexpr int IMP_TB_MIN = 1024;     // the host narrows the tiles down to this ...
+constexpr i64 IMP_GRID_MIN = 1024;   // ... while the grid has fewer blocks than this
+
+template <bool IMPACT>
+__global__ __launch_bounds__(TPB) void k_impact_list(ImpactArgs a, i64 tb) {
+  __shared__ uint32_t once[IMP_TB / 32];
+  __shared__ uint32_t twice[IMP_TB / 32];
+  const i64 c = blockIdx.x;
+  const i64 m = a.mcnt[c];
+  const i64 s0 = a.soffc[c], s = a.soffc[c + 1] - s0;
+  if (m <= 0 || s == 0) return;                  // block-uniform
+  const i64 x0 = (i64)blockIdx.y * tb, x1 = min(x0 + tb, a.UA);
+  const int nw = (int)((x1 - x0 + 31) >> 5);
+  for (int w = threadIdx.x; w < nw; w += TPB) {
+    once[w] = 0u;
+    twice[w] = 0u;
+  }
+  __syncthreads();
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (i64 e = wv; e < s; e += WPB) {
+    const int32_t p = a.slist[s0 + e];
+    const int32_t* L = a.alc + a.alcoff[p];
+    const int32_t cnt = a.nca[p];
+    for (int32_t k = lane; k < cnt; k += 64) {
+      const i64 x = L[k];
+      if (x >= x0 && x < x1) {
+        const int b = (int)(x - x0);
+        const uint32_t bit = 1u << (b & 31);
+        const uint32_t old = atomicOr(&once[b >> 5], bit);
+        if (old & bit) atomicOr(&twice[b >> 5], bit);
+      }
+    }
+  }
+  __syncthreads();
+  for (i64 e = wv; e < s; e += WPB) {
+    const int32_t p = a.slist[s0 + e];
+    const int32_t* L = a.alc + a.alcoff[p];
+    const int32_t cnt = a.nca[p];
+    i64 sum = 0;
+    for (int32_t k = lane; k < cnt; k += 64) {
+      const i64 x = L[k];
+      if (x >= x0 && x < x1) {
+        const int b = (int)(x - x0);
+        if (!((twice[b >> 5] >> (b & 31)) & 1u)) sum += IMPACT && a.cw ? (i64)a.cw[x] : (i64)1;
+      }
+    }
+    sum = wave_sum(sum);
+    if (lane == 0 && sum) {
+      if (IMPACT)
+        atomicAdd(reinterpret_cast<unsigned long long*>(&a.impact[p]),
+                  (unsigned long long)(m * sum));
+      else
+        a.ess[p] = 1;
+    }
+  }
+}
+
+constexpr int IMP_RW = 4;   // AC words per block of the row form
+
+template <bool IMPACT>
+__global__ __launch_bounds__(TPB) void k_impact_rows(ImpactArgs a) {
+  __shared__ u64 so[WPB][IMP_RW];
+  __shared__ u64 st[WPB][IMP_RW];
+  const i64 c = blockIdx.x;
+  const i64 m = a.mcnt[c];
+  const i64 s0 = a.soffc[c], s = a.soffc[c + 1] - s0;
+  if (m <= 0 || s == 0) return;                  // block-uniform
+  const i64 UAW = (a.UA + 63) >> 6;
+  const i64 w0 = (i64)blockIdx.y * IMP_RW;
+  // (bits past UA never count, whatever the caller's last word holds)
+  u64 msk[IMP_RW];
+#pragma unroll
+  for (int k = 0; k < IMP_RW; ++k) {
+    const i64 w = w0 + k;
+    msk[k] = w >= UAW ? 0ull : (w == UAW - 1 && (a.UA & 63)) ? (1ull << (a.UA & 63)) - 1 : ~0ull;
+  }
+  u64 o[IMP_RW], t[IMP_RW];
+#pragma unroll
+  for (int k = 0; k < IMP_RW; ++k) o[k] = t[k] = 0ull;
+  for (i64 e = threadIdx.x; e < s; e += TPB) {
+    const u64* row = a.AC + (i64)a.slist[s0 + e] * a.ldC + w0;
+#pragma unroll
+    for (int k = 0; k < IMP_RW; ++k) {
+      const u64 v = msk[k] ? row[k] & msk[k] : 0ull;
+      t[k] |= o[k] & v;
+      o[k] |= v;
+    }
+  }
+  // two saturating counters join as  twice = t1 | t2 | (o1 & o2), once = o1 | o2
+  for (int d = 32; d >= 1; d >>= 1) {
+#pragma unroll
+    for (int k = 0; k < IMP_RW; ++k) {
+      const u64 o2 = __shfl_xor(o[k], d, 64), t2 = __shfl_xor(t[k], d, 64);
+      t[k] |= t2 | (o[k] & o2);
+      o[k] |= o2;
+    }
+  }
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < IMP_RW; ++k) {
+      so[threadIdx.x >> 6][k] = o[k];
+      st[threadIdx.x >> 6][k] = t[k];
+    }
+  }
+  __syncthreads();
+  u64 uq[IMP_RW];                                // the cells allowed exactly once
+#pragma unroll
+  for (int k = 0; k < IMP_RW; ++k) {
+    u64 O = 0ull, T = 0ull;
+#pragma unroll
+    for (int w = 0; w < WPB; ++w) {
+      T |= st[w][k] | (O & so[w][k]);
+      O |= so[w][k];
+    }
+    uq[k] = O & ~T;
+  }
+  for (i64 e = threadIdx.x; e < s; e += TPB) {
+    const int32_t p = a.slist[s0 + e];
+    const u64* row = a.AC + (i64)p * a.ldC + w0;
+    i64 sum = 0;
+#pragma unroll
+    for (int k = 0; k < IMP_RW; ++k) {
+      u64 v = uq[k] ? row[k] & uq[k] : 0ull;
+      if (IMPACT && a.cw) {
+        while (v) {
+          sum += a.cw[(w0 + k) * 64 + __builtin_ctzll(v)];
+          v &= v - 1;
+        }
+      } else {
+        sum += __popcll(v);
+      }
+    }
+    if (sum) {
+      if (IMPACT)
+        atomicAdd(reinterpret_cast<unsigned long long*>(&a.impact[p]),
+                  (unsigned long long)(m * sum));
+      else
+        a.ess[p] = 1;
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------
 // policy_shadow's pair count without the pairs (kano_verify, shadow_cap < 0):
 // algorithm.py:58-80 counts, per pod i, the ordered pairs j != k of S(i) with

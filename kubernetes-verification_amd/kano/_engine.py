@@ -603,6 +603,22 @@ class DeviceBuild:
                   "kano_conflict_classes")
         return off, pairs, members
 
+    # -- policy_impact / policy_redundant (kano_policy_impact) -----------
+    def policy_impact(self) -> np.ndarray:
+        """impact[p]: the pod pairs (i, j), i in this context's rows, that only
+        policy p allows -- what removing p alone takes away.  int64, length P."""
+        out = np.zeros(self.info()["P"], dtype=np.int64)
+        self._chk(self.lib.kano_policy_impact(self.ctx, 0, _ptr(out), None, None),
+                  "kano_policy_impact")
+        return out
+
+    def policy_essential(self) -> np.ndarray:
+        """essential[p]: impact[p] > 0, without the sums.  bool, length P."""
+        out = np.zeros(self.info()["P"], dtype=np.uint8)
+        self._chk(self.lib.kano_policy_impact(self.ctx, 1, None, _ptr(out), None),
+                  "kano_policy_impact")
+        return out.astype(bool)
+
     def rows_timing(self, reset: bool = False) -> dict:
         """k_rows launch times (HIP events) since the last reset: sum, count,
         min, max (ms); waits for the context's work."""
@@ -661,7 +677,7 @@ class DeviceBuild:
         self._chk(self.lib.kano_stage_times(self.ctx, _ptr(ms)), "kano_stage_times")
         return dict(classes=float(ms[0]), allow=float(ms[1]), select=float(ms[2]),
                     rows=float(ms[3]), shadow=float(ms[4]), build=float(ms[5]),
-                    k_rows=float(ms[6]))
+                    k_rows=float(ms[6]), impact=float(ms[7]))
 
 
 def shadow_from_lists(n_lists: int, nbits: int, soff: np.ndarray, slist: np.ndarray,
@@ -706,5 +722,31 @@ def conflict_from_lists(n_lists: int, nbits: int, soff: np.ndarray, slist: np.nd
         out = np.zeros((int(cnt.value), 2), dtype=np.int32)
         b._chk(lib.kano_conflict_fetch(b.ctx, _ptr(out)), "kano_conflict_fetch")
         return out
+    finally:
+        b.close()
+
+
+def impact_from_lists(n_lists: int, nbits: int, soff: np.ndarray, slist: np.ndarray,
+                      allow_words: np.ndarray, device: int = 0, flags_only: bool = False,
+                      mode: Optional[int] = None) -> np.ndarray:
+    """policy_impact over explicit per-container policy lists and allow sets
+    (kano_policy_impact_lists): impact[p] as int64 of length P, or with
+    ``flags_only`` the essential flags (impact > 0) as bool.  The ids within
+    one list must be distinct.  ``mode`` passes a raw mode to the entry point."""
+    lib = nat.load()
+    b = DeviceBuild(None, device=device)
+    try:
+        P = allow_words.shape[0]
+        soff = np.ascontiguousarray(soff, dtype=np.int64)
+        slist = np.ascontiguousarray(slist, dtype=np.int32)
+        aw = np.ascontiguousarray(allow_words, dtype=np.uint64)
+        if mode is None:
+            mode = 1 if flags_only else 0
+        impact = np.zeros(P, dtype=np.int64)
+        ess = np.zeros(P, dtype=np.uint8)
+        b._chk(lib.kano_policy_impact_lists(b.ctx, int(n_lists), int(nbits), int(P), _ptr(soff),
+                                            _ptr(slist), _ptr(aw), int(mode), _ptr(impact),
+                                            _ptr(ess), None), "kano_policy_impact_lists")
+        return ess.astype(bool) if mode == 1 else impact
     finally:
         b.close()

@@ -54,6 +54,9 @@ SIGNATURES = {
     "kano_conflict_lists": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                                     c_void_p, c_int, POINTER(c_int64)]),
     "kano_conflict_classes": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "kano_policy_impact": (c_int, [c_void_p, c_int, c_void_p, c_void_p, POINTER(c_int64)]),
+    "kano_policy_impact_lists": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                         c_void_p, c_int, c_void_p, c_void_p, POINTER(c_int64)]),
     "kano_verify": (c_int, [c_void_p, c_int, c_void_p, c_int32, c_int64, c_void_p, c_void_p,
                             c_void_p, c_int64, POINTER(c_int64)]),
     "kano_verify_shard": (c_int, [c_void_p, c_int, c_void_p, c_int32, c_int64, c_int, c_void_p]),

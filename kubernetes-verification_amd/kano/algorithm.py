@@ -271,6 +271,77 @@ def policy_conflict_summary(matrix: ReachabilityMatrix, policies: List[Policy],
 
 
 # ---------------------------------------------------------------------------
+# What removing a policy changes.  Not part of kano_py's algorithm.py.  With
+# cover(i, j) = #{p : i in working_select_set_p, j in working_allow_set_p},
+#   impact[p] = #{(i, j) : i in select_p, j in allow_p, cover(i, j) == 1}
+# is the number of pod pairs that lose reachability when p alone is removed,
+# and p is redundant when impact[p] == 0: an empty select or allow set, a
+# policy covered by the union of others (policy_shadow sees only the cover by
+# one other policy), each of two identical policies.  Defined over the sets,
+# so accumulated or edited select_policies lists (quirk Q5) do not change it.
+
+def _set_lists(policies: List[Policy], containers: List[Container]):
+    """The general form's inputs from the policies' working sets: per
+    container the ascending, distinct ids of the policies selecting it, and
+    each policy's allow words, as (n_lists, nbits, soff, flat int32, words)."""
+    P, n = len(policies), len(containers)
+    pods, nbits = [], None
+    for p, pol in enumerate(policies):
+        sel, alw = pol.working_select_set, pol.working_allow_set
+        if sel is None or alw is None:
+            raise ValueError(f"policy {p} has no working sets (build a matrix with it first)")
+        if len(sel) != n:
+            raise ValueError(f"policy {p}: working_select_set has {len(sel)} bits for "
+                             f"{n} containers")
+        if nbits is None:
+            nbits = len(alw)
+        elif len(alw) != nbits:
+            raise ValueError("bitarrays of equal length expected for bitwise operation")
+        b = sel if isinstance(sel, BitArray) else BitArray(sel)
+        pods.append(set_bit_indices(b.words(), n))
+    nbits = nbits or 0
+    W = (nbits + 63) >> 6
+    aw = np.zeros((P, W), dtype=np.uint64)
+    for p, pol in enumerate(policies):
+        s = pol.working_allow_set
+        b = s if isinstance(s, BitArray) else BitArray(s)
+        aw[p] = b.words()[:W]
+    if W and nbits & 63:
+        aw[:, -1] &= np.uint64((1 << (nbits & 63)) - 1)
+    # (policy-major entries, a stable counting sort by pod: every list ascending)
+    key = np.concatenate(pods) if pods else np.zeros(0, np.int64)
+    ids = np.repeat(np.arange(P, dtype=np.int32), [x.size for x in pods])
+    soff = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(key, minlength=n), out=soff[1:])
+    flat = ids[np.argsort(key, kind="stable")]
+    return n, nbits, soff, flat, aw
+
+
+def policy_impact(matrix: ReachabilityMatrix, policies: List[Policy],
+                  containers: List[Container]) -> np.ndarray:
+    """impact[p] for every policy: int64 array of length len(policies)."""
+    if _fast_path(matrix, policies, containers):
+        return _engine(matrix).policy_impact()
+    from ._engine import impact_from_lists
+    n_lists, nbits, soff, flat, aw = _set_lists(policies, containers)
+    return impact_from_lists(n_lists, nbits, soff, flat, aw, device=_engine(matrix).device)
+
+
+def policy_redundant(matrix: ReachabilityMatrix, policies: List[Policy],
+                     containers: List[Container]) -> List[int]:
+    """Ascending indices of the policies whose removal changes no pair (the
+    flags alone: no sums on the device)."""
+    if _fast_path(matrix, policies, containers):
+        ess = _engine(matrix).policy_essential()
+    else:
+        from ._engine import impact_from_lists
+        n_lists, nbits, soff, flat, aw = _set_lists(policies, containers)
+        ess = impact_from_lists(n_lists, nbits, soff, flat, aw, device=_engine(matrix).device,
+                                flags_only=True)
+    return np.flatnonzero(~ess).tolist()
+
+
+# ---------------------------------------------------------------------------
 # Multi-hop reachability (SURVEY.md §8(f) rank 3).  Not part of kano_py's
 # algorithm.py: kubesv's `path` relation (kubesv/kubesv/constraint.py:233-237,
 # path(src, dst) :- edge(src, dst); path(src, dst) :- edge(src, sel),

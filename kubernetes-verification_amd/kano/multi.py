@@ -316,6 +316,15 @@ class MultiBuild:
     def conflict_count(self) -> int:
         return sum(m.conflict_count() for m in self.members)
 
+    def policy_impact(self) -> np.ndarray:
+        """impact[p] over all rows: the members' impacts (each over its own
+        rows) summed."""
+        return np.sum([m.policy_impact() for m in self.members], axis=0, dtype=np.int64)
+
+    def policy_essential(self) -> np.ndarray:
+        """essential[p]: the members' flags OR-ed."""
+        return np.any([m.policy_essential() for m in self.members], axis=0)
+
     # -- matrix access: owners --------------------------------------------
     def rows(self, r0: int, nrows: int, out: Optional[np.ndarray] = None) -> np.ndarray:
         if out is None:
