@@ -217,6 +217,45 @@ int kano_policy_impact_lists(kano_ctx* ctx, int64_t n_lists, int64_t nbits, int6
                              const uint64_t* allow_rows, int mode,
                              int64_t* impact, uint8_t* essential, int64_t* n_redundant);
 
+/* matrix_diff: what a change adds and removes.  a and b hold matrices of the
+ * same n on the same device over the same rows r0..r1 (built, loaded, path or
+ * edge matrices alike); for i in [r0, r1), j in [0, n):
+ *   added(i,j) = B[i,j] and not A[i,j],   removed(i,j) = A[i,j] and not B[i,j].
+ * Bits at positions >= n of a row's last word (kano_put_rows copies them
+ * unmasked) belong to neither matrix.  One pass over both matrices on b's
+ * stream, after a's pending work; errors are reported on b.  Exact integers.
+ * totals[2] = the added and removed bits; row_added / row_removed (rows_local
+ * int32 each) the counts per local row; col_added / col_removed (W words
+ * each, tail-masked) bit j set when column j gained / lost at least one
+ * source.  Any of the four arrays may be NULL; with all four NULL only the
+ * totals are computed.  a == b gives an empty diff; n == 0 or no local rows
+ * gives zeros.  -EINVAL: a NULL context or totals, two devices, different n,
+ * different rows.  Neither matrix, nor any class table or check result of
+ * either context, changes; both contexts stay usable after an error.  The
+ * totals of row shards add up, their row counts concatenate, their column
+ * words OR. */
+int kano_diff(kano_ctx* a, kano_ctx* b, int64_t* totals /* 2: added, removed */,
+              int32_t* row_added, int32_t* row_removed,    /* rows_local each, or NULL */
+              uint64_t* col_added, uint64_t* col_removed); /* W words each, or NULL */
+/* The pairs of one kind (0 added, 1 removed) in rows [r0, r0 + nrows) of this
+ * shard, as (i, j) int32 with global indices, ascending by i and then j.
+ * Self-contained: the call recounts its row range.  *count is always set (0
+ * on an argument error); pairs NULL asks for the count alone.  With pairs
+ * given and count > max_pairs the call returns -ENOSPC and writes no pair.
+ * -EINVAL as kano_diff, and for a kind outside {0, 1}, a row range outside
+ * the shard, a NULL count or max_pairs < 0; -ENOTSUP past 4,194,304 rows in
+ * one call (split the range). */
+int kano_diff_pairs(kano_ctx* a, kano_ctx* b, int kind /* 0 added, 1 removed */,
+                    int64_t r0, int64_t nrows, int64_t max_pairs,
+                    int64_t* count, int32_t* pairs /* 2*count, or NULL: count only */);
+/* dst's rows := src's rows, device to device (dst: a matrix of the same n and
+ * rows, e.g. a context with no policies).  dst is then an edited matrix, as
+ * after kano_import_rows.  src == dst returns -EINVAL. */
+int kano_copy_matrix(kano_ctx* src, kano_ctx* dst);
+/* The last kano_diff's device time on this (its second) context, fill and
+ * kernel without the copies, in ms; recorded under KANO_TUNE=timing=1, else 0. */
+int kano_diff_time(kano_ctx* ctx, float* ms);
+
 /* The whole verification pass in one call (the sequence kano_py's
  * sample/example.py and tests/test_basic.py run: build_matrix, then
  * all_reachable, all_isolated, user_crosscheck, system_isolation and

@@ -164,6 +164,7 @@ struct kano_ctx {
   int rows_cww = MAX_CWW_KNOB;   // cww: k_rows column chunk (words); the chunking wide matrices
                              // (n > 524k) take, forced at small n
   int impact_form = 0;       // impf=1/2: policy_impact's list / row form forced (0: by density)
+  int diff_grid = 0;         // dgrid=K: at most K blocks for k_diff_rows (0: every resident block)
   int shadow_r = 0;          // shr=1/2/4/8: k_shadow_test1s's 256-pair rounds per block (0: auto)
   int shg_sub_lds = 1;       // shgsub=0: forces k_shg_sub's word-by-word row compare (the
                              // form rows wider than 64 KB of LDS take)
@@ -254,6 +255,11 @@ struct kano_ctx {
   // sums and essential flags, no other buffer written
   DBuf impact_out, impact_ess;
   float impact_ms = 0.f;      // timing=1: the last call's device time (fill + kernel)
+  // matrix_diff (kano_diff / kano_diff_pairs, in the second context b): the
+  // totals, column words and row counts of the last call, no other buffer
+  // written (the offsets and pairs of kano_diff_pairs are temporaries)
+  DBuf diff_buf;
+  float diff_ms = 0.f;        // timing=1: the last kano_diff's fill + kernel (kano_diff_time)
   // policy_shadow count-only (kano_verify with shadow_cap < 0): the grouped
   // count (k_shg_*) instead of the pair-by-pair flags
   bool vs_count_only = false;
@@ -403,6 +409,22 @@ int sync(kano_ctx* ctx);
 int ensure_built(kano_ctx* ctx);
 int ensure_matrix(kano_ctx* ctx);
 i64 rows_local(const kano_ctx* ctx);
+
+// matrix_diff's launches (kano_hip.hip, next to the kernels; the entry points
+// are kano_ext.hip's)
+struct DiffOut {
+  u64* totals;              // added, removed
+  int32_t* row_added;       // NULL: the totals alone
+  int32_t* row_removed;
+  u64* col_added;
+  u64* col_removed;
+};
+constexpr int DIFF_SCAN_TILES = 2048;   // row tiles of one offset scan (4M rows)
+int diff_rows_launch(kano_ctx* ctx, const u64* A, i64 ldA, const u64* B, i64 ldB, i64 rows,
+                     const DiffOut& o);
+int diff_offsets_launch(kano_ctx* ctx, const int32_t* cnt, i64 rows, i64* tmp, i64* off);
+int diff_emit_launch(kano_ctx* ctx, const u64* A, i64 ldA, const u64* B, i64 ldB, i64 rows,
+                     int kind, i64 row0, const i64* off, i64 cap, int32_t* pairs);
 
 template <typename T>
 T* P_(DBuf& b) {

@@ -711,3 +711,202 @@ int kano_k8s_edge(kano_ctx* in_t, kano_ctx* eg_t, kano_ctx* dst, int flags, int6
 }
 
 }  // extern "C"
+
+// ===========================================================================
+// matrix_diff: two resident matrices compared in one pass (k_diff_rows /
+// k_diff_emit, kano_kernels.hpp; launched through kano_hip.hip's helpers).
+// ===========================================================================
+namespace {
+
+// kano_path's preamble for two contexts holding the same rows: both matrices
+// present, a's pending work complete; the work then runs on b's stream and
+// errors are reported on b
+int diff_prepare(kano_ctx* a, kano_ctx* b, const char* what) {
+  kano_ctx* ctx = b;
+  const std::string w(what);
+  if (a->device != b->device) return fail(b, -EINVAL, w + ": contexts on two devices");
+  KCHK(hipSetDevice(b->device));
+  if (a != b) {
+    const int rc = ensure_matrix(a);
+    if (rc) return fail(b, rc, w + ": first matrix: " + a->err);
+  }
+  KTRY(ensure_matrix(b));
+  if (a->n != b->n) return fail(b, -EINVAL, w + ": the matrices differ in size");
+  if (a->r0 != b->r0 || a->r1 != b->r1)
+    return fail(b, -EINVAL, w + ": the contexts hold different rows");
+  if ((a->ldM | b->ldM) & 1) return fail(b, -ENOTSUP, w + ": odd row pitch");
+  if (a != b) {
+    const int rc = sync(a);
+    if (rc) return fail(b, rc, w + ": first matrix: " + a->err);
+  }
+  return 0;
+}
+
+// diff_buf's layout for `rows` rows: [totals 2 | col_added W | col_removed W]
+// u64, then [row_added | row_removed] int32
+struct DiffBuf {
+  u64* totals;
+  u64* col;
+  int32_t* row;
+  size_t bytes;
+};
+DiffBuf diff_layout(kano_ctx* b, i64 rows, bool full) {
+  DiffBuf d;
+  const size_t words = 2 + (full ? 2 * (size_t)b->W : 0);
+  d.bytes = sizeof(u64) * words + (full ? sizeof(int32_t) * 2 * (size_t)rows : 0);
+  d.totals = P_<u64>(b->diff_buf);
+  d.col = d.totals + 2;
+  d.row = reinterpret_cast<int32_t*>(d.totals + words);
+  return d;
+}
+
+// the pass over rows [q0, q0 + rows) of both matrices into b->diff_buf
+int diff_pass(kano_ctx* a, kano_ctx* b, i64 q0, i64 rows, bool full, DiffBuf* out) {
+  kano_ctx* ctx = b;
+  KTRY(dalloc(ctx, b->diff_buf, diff_layout(b, rows, full).bytes));
+  const DiffBuf d = diff_layout(b, rows, full);
+  KCHK(hipMemsetAsync(b->diff_buf.p, 0, d.bytes, ctx->stream));
+  DiffOut o{};
+  o.totals = d.totals;
+  if (full) {
+    o.col_added = d.col;
+    o.col_removed = d.col + b->W;
+    o.row_added = d.row;
+    o.row_removed = d.row + rows;
+  }
+  KTRY(diff_rows_launch(ctx, P_<u64>(a->M) + (q0 - a->r0) * a->ldM, a->ldM,
+                        P_<u64>(b->M) + (q0 - b->r0) * b->ldM, b->ldM, rows, o));
+  *out = d;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kano_diff(kano_ctx* a, kano_ctx* b, int64_t* totals, int32_t* row_added,
+              int32_t* row_removed, uint64_t* col_added, uint64_t* col_removed) {
+  if (!a || !b) return -EINVAL;
+  kano_ctx* ctx = b;
+  if (!totals) return fail(b, -EINVAL, "kano_diff: totals is NULL");
+  KTRY(diff_prepare(a, b, "kano_diff"));
+  const i64 rl = rows_local(b), W = b->W;
+  totals[0] = totals[1] = 0;
+  if (rl > 0) {
+    if (row_added) std::memset(row_added, 0, sizeof(int32_t) * (size_t)rl);
+    if (row_removed) std::memset(row_removed, 0, sizeof(int32_t) * (size_t)rl);
+  }
+  if (W > 0) {
+    if (col_added) std::memset(col_added, 0, sizeof(u64) * (size_t)W);
+    if (col_removed) std::memset(col_removed, 0, sizeof(u64) * (size_t)W);
+  }
+  if (rl <= 0 || W <= 0) return 0;
+  const bool full = row_added || row_removed || col_added || col_removed;
+  // timing=1: the call's device time (the fill and the kernel, no copy)
+  hipEvent_t tev[2] = {nullptr, nullptr};
+  if (ctx->stage_timing) {
+    KCHK(hipEventCreate(&tev[0]));
+    KCHK(hipEventCreate(&tev[1]));
+    KCHK(hipEventRecord(tev[0], ctx->stream));
+  }
+  DiffBuf d{};
+  KTRY(diff_pass(a, b, b->r0, rl, full, &d));
+  if (tev[0]) {
+    KCHK(hipEventRecord(tev[1], ctx->stream));
+    KCHK(hipEventSynchronize(tev[1]));
+    (void)hipEventElapsedTime(&ctx->diff_ms, tev[0], tev[1]);
+    (void)hipEventDestroy(tev[0]);
+    (void)hipEventDestroy(tev[1]);
+  }
+  u64 t[2] = {0, 0};
+  KCHK(hipMemcpyAsync(t, d.totals, sizeof(t), hipMemcpyDeviceToHost, ctx->stream));
+  if (row_added)
+    KCHK(hipMemcpyAsync(row_added, d.row, sizeof(int32_t) * rl, hipMemcpyDeviceToHost,
+                        ctx->stream));
+  if (row_removed)
+    KCHK(hipMemcpyAsync(row_removed, d.row + rl, sizeof(int32_t) * rl, hipMemcpyDeviceToHost,
+                        ctx->stream));
+  if (col_added)
+    KCHK(hipMemcpyAsync(col_added, d.col, sizeof(u64) * W, hipMemcpyDeviceToHost, ctx->stream));
+  if (col_removed)
+    KCHK(hipMemcpyAsync(col_removed, d.col + W, sizeof(u64) * W, hipMemcpyDeviceToHost,
+                        ctx->stream));
+  KTRY(sync(ctx));
+  totals[0] = (int64_t)t[0];
+  totals[1] = (int64_t)t[1];
+  return 0;
+}
+
+int kano_diff_pairs(kano_ctx* a, kano_ctx* b, int kind, int64_t r0, int64_t nrows,
+                    int64_t max_pairs, int64_t* count, int32_t* pairs) {
+  if (!a || !b) return -EINVAL;
+  kano_ctx* ctx = b;
+  if (!count) return fail(b, -EINVAL, "kano_diff_pairs: count is NULL");
+  *count = 0;
+  if (kind != 0 && kind != 1) return fail(b, -EINVAL, "kano_diff_pairs: unknown kind");
+  if (max_pairs < 0) return fail(b, -EINVAL, "kano_diff_pairs: max_pairs < 0");
+  KTRY(diff_prepare(a, b, "kano_diff_pairs"));
+  if (nrows < 0 || r0 < b->r0 || r0 > b->r1 || nrows > b->r1 - r0)
+    return fail(b, -EINVAL, "kano_diff_pairs: rows outside this shard");
+  if (nrows == 0 || b->W == 0) return 0;
+  // the range recounted: its row counts are the emission's offsets
+  DiffBuf d{};
+  KTRY(diff_pass(a, b, r0, nrows, true, &d));
+  u64 t[2] = {0, 0};
+  KCHK(hipMemcpyAsync(t, d.totals, sizeof(t), hipMemcpyDeviceToHost, ctx->stream));
+  KTRY(sync(ctx));
+  const i64 total = (i64)t[kind];
+  *count = total;
+  if (!pairs || total == 0) return 0;
+  if (total > max_pairs)
+    return fail(b, -ENOSPC, "kano_diff_pairs: " + std::to_string(total) + " pairs, room for " +
+                                std::to_string(max_pairs));
+  DBuf off, out;
+  auto run = [&]() -> int {
+    KTRY(dalloc(ctx, off, sizeof(i64) * (size_t)(nrows + 1 + 2 * DIFF_SCAN_TILES + 1)));
+    KTRY(dalloc(ctx, out, sizeof(int32_t) * 2 * (size_t)total));
+    i64* offp = P_<i64>(off);
+    KTRY(diff_offsets_launch(ctx, d.row + (kind ? nrows : 0), nrows, offp + nrows + 1, offp));
+    KTRY(diff_emit_launch(ctx, P_<u64>(a->M) + (r0 - a->r0) * a->ldM, a->ldM,
+                          P_<u64>(b->M) + (r0 - b->r0) * b->ldM, b->ldM, nrows, kind, r0, offp,
+                          total, P_<int32_t>(out)));
+    KCHK(hipMemcpyAsync(pairs, out.p, sizeof(int32_t) * 2 * (size_t)total, hipMemcpyDeviceToHost,
+                        ctx->stream));
+    return sync(ctx);
+  };
+  const int rc = run();
+  if (rc) (void)hipStreamSynchronize(ctx->stream);   // nothing in flight on the temporaries
+  dfree(off);
+  dfree(out);
+  return rc;
+}
+
+int kano_copy_matrix(kano_ctx* src, kano_ctx* dst) {
+  if (!src || !dst) return -EINVAL;
+  kano_ctx* ctx = dst;
+  if (src == dst)
+    return fail(dst, -EINVAL, "kano_copy_matrix: the destination must be another context");
+  KTRY(diff_prepare(src, dst, "kano_copy_matrix"));
+  const i64 rl = rows_local(dst), W = dst->W;
+  if (rl > 0 && W > 0) {
+    if (src->ldM == dst->ldM)
+      KCHK(hipMemcpyAsync(dst->M.p, src->M.p, sizeof(u64) * rl * dst->ldM,
+                          hipMemcpyDeviceToDevice, ctx->stream));
+    else
+      KCHK(hipMemcpy2DAsync(dst->M.p, sizeof(u64) * dst->ldM, src->M.p, sizeof(u64) * src->ldM,
+                            sizeof(u64) * W, (size_t)rl, hipMemcpyDeviceToDevice, ctx->stream));
+  }
+  KTRY(sync(dst));
+  dst->cols_valid = false;
+  dst->rows_dirty = true;
+  dst->user_edited = true;
+  return 0;
+}
+
+int kano_diff_time(kano_ctx* ctx, float* ms) {
+  if (!ctx || !ms) return -EINVAL;
+  *ms = ctx->diff_ms;
+  return 0;
+}
+
+}  // extern "C"

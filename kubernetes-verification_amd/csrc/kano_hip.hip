@@ -2060,6 +2060,99 @@ int crosscheck_impl(kano_ctx* ctx, const int32_t* gid, int32_t ngroups = 0) {
   return 0;
 }
 
+// matrix_diff's launches (k_diff_rows, k_diff_emit: kano_kernels.hpp) for the
+// entry points in kano_ext.hip, on ctx's stream.  The outputs of
+// diff_rows_launch are zero before it; with o.row_added NULL it runs the
+// totals-only instantiation.
+int diff_rows_launch(kano_ctx* ctx, const u64* A, i64 ldA, const u64* B, i64 ldB, i64 rows,
+                     const DiffOut& o) {
+  const i64 W = ctx->W;
+  if (rows <= 0 || W <= 0) return 0;
+  const bool full = o.row_added != nullptr;
+  DiffArgs a{};
+  a.A = A;
+  a.ldA = ldA;
+  a.B = B;
+  a.ldB = ldB;
+  a.rows = rows;
+  a.W = W;
+  a.n = ctx->n;
+  // equal chunks of at most DIFF_CW words, whole 128-byte lines each
+  const i64 nch = (W + DIFF_CW - 1) / DIFF_CW;
+  a.cw = std::min<i64>(DIFF_CW, ((W + nch - 1) / nch + 15) / 16 * 16);
+  a.nrg = (rows + DIFF_ROWS - 1) / DIFF_ROWS;
+  a.items = a.nrg * ((W + a.cw - 1) / a.cw);
+  a.row_added = o.row_added;
+  a.row_removed = o.row_removed;
+  a.col_added = o.col_added;
+  a.col_removed = o.col_removed;
+  a.totals = o.totals;
+  // every block resident (the occupancy the register count admits), each
+  // striding over the items: a block flushes a column word at most once
+  static int per_cu[2] = {0, 0};
+  if (!per_cu[full]) {
+    int nb = 0;
+    const hipError_t e =
+        full ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_diff_rows<true>, TPB, 0)
+             : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_diff_rows<false>, TPB, 0);
+    per_cu[full] = (e == hipSuccess && nb > 0) ? std::min(nb, 8) : 4;
+  }
+  const i64 cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
+  i64 blocks = std::min<i64>(a.items, cus * per_cu[full]);
+  if (ctx->diff_grid > 0) blocks = std::min<i64>(blocks, ctx->diff_grid);
+  const unsigned grid = (unsigned)blocks;
+  if (full) hipLaunchKernelGGL((k_diff_rows<true>), dim3(grid), dim3(TPB), 0, ctx->stream, a);
+  else hipLaunchKernelGGL((k_diff_rows<false>), dim3(grid), dim3(TPB), 0, ctx->stream, a);
+  KLAUNCH();
+  return 0;
+}
+
+// off[0 .. rows] = the exclusive scan of cnt (int32, rows entries); tmp holds
+// 2 * DIFF_SCAN_TILES + 1 i64.  Two levels of k_scan_sums / k_scan_tiles.
+int diff_offsets_launch(kano_ctx* ctx, const int32_t* cnt, i64 rows, i64* tmp, i64* off) {
+  const i64 tiles = (rows + SCAN_TILE - 1) / SCAN_TILE;
+  if (tiles > DIFF_SCAN_TILES)
+    return fail(ctx, -ENOTSUP, "kano_diff_pairs: more than " +
+                                   std::to_string((i64)DIFF_SCAN_TILES * SCAN_TILE) +
+                                   " rows in one call");
+  const i64* tile_off = nullptr;
+  if (tiles > 1) {
+    hipLaunchKernelGGL((k_scan_sums<int32_t, i64>), dim3((unsigned)tiles), dim3(TPB), 0,
+                       ctx->stream, cnt, rows, tmp);
+    KLAUNCH();
+    hipLaunchKernelGGL((k_scan_tiles<i64, i64>), dim3(1), dim3(TPB), 0, ctx->stream,
+                       (const i64*)tmp, tiles, (const i64*)nullptr, tmp + DIFF_SCAN_TILES);
+    KLAUNCH();
+    tile_off = tmp + DIFF_SCAN_TILES;
+  }
+  hipLaunchKernelGGL((k_scan_tiles<int32_t, i64>), dim3((unsigned)tiles), dim3(TPB), 0,
+                     ctx->stream, cnt, rows, tile_off, off);
+  KLAUNCH();
+  return 0;
+}
+
+int diff_emit_launch(kano_ctx* ctx, const u64* A, i64 ldA, const u64* B, i64 ldB, i64 rows,
+                     int kind, i64 row0, const i64* off, i64 cap, int32_t* pairs) {
+  DiffEmitArgs a{};
+  a.A = A;
+  a.ldA = ldA;
+  a.B = B;
+  a.ldB = ldB;
+  a.rows = rows;
+  a.W = ctx->W;
+  a.n = ctx->n;
+  a.kind = kind;
+  a.row0 = row0;
+  a.off = off;
+  a.cap = cap;
+  a.pairs = pairs;
+  // a wave per row, grid-stride past 2^20 blocks (grid.x limit)
+  const unsigned grid = (unsigned)std::min<i64>(nblk(rows, TPB / 64), 1 << 20);
+  hipLaunchKernelGGL(k_diff_emit, dim3(grid), dim3(TPB), 0, ctx->stream, a);
+  KLAUNCH();
+  return 0;
+}
+
 }  // namespace kano_eng
 
 using namespace kano_eng;
@@ -2127,6 +2220,7 @@ int kano_create(int device, kano_ctx** out) {
         if (k == "pathtn" && (v == 2 || v == 4)) ctx->path_tn = v;
         if (k == "shgsub") ctx->shg_sub_lds = v;
         if (k == "impf" && v >= 0 && v <= 2) ctx->impact_form = v;
+        if (k == "dgrid" && v >= 0) ctx->diff_grid = v;
         if (k == "shr" && (v == 1 || v == 2 || v == 4 || v == 8)) ctx->shadow_r = v;
         if (k == "rcu" && v >= 0 && v <= 28 && (v < 4 || v % 4 == 0)) ctx->rows_cu_off = v;
         if (k == "rcubytes" && v >= 0) ctx->rows_cu_bytes = (i64)v << 30;
@@ -2302,7 +2396,7 @@ void kano_destroy(kano_ctx* ctx) {
                   &ctx->A2,     &ctx->own,     &ctx->cross,   &ctx->gmin,      &ctx->gmax,
                   &ctx->flags,  &ctx->T,       &ctx->loff,    &ctx->L,         &ctx->tp,
                   &ctx->poff,   &ctx->out,     &ctx->conflict_out, &ctx->scratch_words, &ctx->ident, &ctx->ecls,
-                  &ctx->impact_out, &ctx->impact_ess,
+                  &ctx->impact_out, &ctx->impact_ess, &ctx->diff_buf,
                   &ctx->tcnt,   &ctx->toff,    &ctx->sizes,   &ctx->icnt,      &ctx->ioff,
                   &ctx->sysrow, &ctx->wicls,   &ctx->idxd,
                   &ctx->ckey,   &ctx->corder,  &ctx->kcnt,    &ctx->koff,

@@ -3731,4 +3731,216 @@ __global__ __launch_bounds__(TPB) void k_idx_write(IdxRows a, const i64* __restr
   if (bit) idx[pos] = (int32_t)j;
 }
 
+// ===========================================================================
+// matrix_diff: what B holds and A does not (added = B & ~A) and the reverse
+// (removed = A & ~B), over two matrices of the same n and rows.  Not part of
+// kano_py; the host restatement is tests/test_diff.py's.
+//
+// k_diff_rows makes the one pass.  A work item is DIFF_ROWS rows of one
+// column chunk of cw <= DIFF_CW words (the host splits W into equal chunks,
+// a multiple of 16 words each: a narrow last chunk would leave every block a
+// latency-bound tail of items with next to no bytes); inside it wave w takes
+// rows w, w + 4, ..., and a lane the word pairs lane * 2 + 128 k of the
+// chunk, so a wave reads 1 KiB of A and 1 KiB of B per instruction, 16 bytes
+// a lane, and every word of either matrix is read by exactly one lane, once.
+// The items are numbered
+// chunk-major and a block takes items blockIdx.x, + gridDim.x, ...: its
+// chunk never decreases, so the column words a block has seen stay in
+// registers (DIFF_K word pairs per kind and lane) until the chunk changes or
+// the block ends, then go through LDS (the four waves OR-ed) into one global
+// atomicOr per non-zero word -- a word of the column result is flushed by a
+// block at most once.  Row counts: the lane's popcounts of one row (at most
+// 512 bits of either kind, packed 16 + 16 into one register: a wave's row
+// holds DIFF_CW * 64 = 32768 <= 0xffff), one wave_sum, one atomicAdd per
+// non-zero (row, chunk, kind).  Totals: every wave adds its row sums into
+// 64-bit registers from the first one on, the block adds its waves' in LDS,
+// one 64-bit atomicAdd per block and kind.
+// FULL = false: the totals alone (no row or column result is written).
+// The outputs are zero before the launch.  Bits at positions >= n of a row's
+// last word are masked; the pitch beyond W words is not read.
+// ===========================================================================
+constexpr int DIFF_K = 4;                // 16-byte loads per lane, row and matrix
+constexpr int DIFF_CW = 128 * DIFF_K;    // words of a column chunk
+constexpr int DIFF_ROWS = 16;            // rows of a work item (4 per wave)
+static_assert((i64)DIFF_CW * 64 <= 0xffff, "a wave's row count must fit 16 bits");
+
+struct DiffArgs {
+  const u64* A;
+  i64 ldA;
+  const u64* B;
+  i64 ldB;
+  i64 rows, W, n;
+  i64 cw;                   // words of a column chunk: even, <= DIFF_CW
+  i64 nrg;                  // row groups: ceil(rows / DIFF_ROWS)
+  i64 items;                // nrg * ceil(W / cw)
+  int32_t* row_added;       // rows each
+  int32_t* row_removed;
+  u64* col_added;           // W each
+  u64* col_removed;
+  u64* totals;              // added, removed
+};
+
+// one item's rows for this wave, words [c0, wend) (wend = the chunk's end or
+// W).  A lane loads 16 bytes of either matrix where both words lie below
+// wend, 8 where only the first does (an odd W's last word), nothing past it:
+// the predicates are lane masks around the loads, all issued before the first
+// wait.  valid_mask clears the tail bits.
+template <bool FULL>
+__device__ __forceinline__ void diff_item(const DiffArgs& a, i64 c0, i64 wend, i64 r0,
+                                          u64 (&ca)[2 * DIFF_K], u64 (&cr)[2 * DIFF_K], i64& ta,
+                                          i64& tr) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const i64 w0 = c0 + lane * 2;
+  const i64 rend = min(a.rows, r0 + DIFF_ROWS);
+#pragma unroll 1
+  for (i64 r = r0 + wid; r < rend; r += TPB / 64) {
+    const u64* pa = a.A + r * a.ldA + w0;
+    const u64* pb = a.B + r * a.ldB + w0;
+    u64x2 va[DIFF_K], vb[DIFF_K];
+#pragma unroll
+    for (int k = 0; k < DIFF_K; ++k) {
+      const i64 w = w0 + 128 * k;
+      va[k] = u64x2{0ull, 0ull};
+      vb[k] = u64x2{0ull, 0ull};
+      if (w + 1 < wend) {
+        va[k] = *reinterpret_cast<const u64x2*>(pa + 128 * k);
+        vb[k] = *reinterpret_cast<const u64x2*>(pb + 128 * k);
+      } else if (w < wend) {
+        va[k].x = pa[128 * k];
+        vb[k].x = pb[128 * k];
+      }
+    }
+    uint32_t cnt = 0;   // added | removed << 16
+#pragma unroll
+    for (int k = 0; k < DIFF_K; ++k) {
+      const i64 w = w0 + 128 * k;
+      const u64 m0 = valid_mask(w, a.n), m1 = valid_mask(w + 1, a.n);
+      const u64 x0 = (va[k].x ^ vb[k].x) & m0, x1 = (va[k].y ^ vb[k].y) & m1;
+      const u64 ad0 = x0 & vb[k].x, ad1 = x1 & vb[k].y, rm0 = x0 & va[k].x, rm1 = x1 & va[k].y;
+      cnt += (uint32_t)(__popcll(ad0) + __popcll(ad1)) +
+             ((uint32_t)(__popcll(rm0) + __popcll(rm1)) << 16);
+      if (FULL) {
+        ca[2 * k] |= ad0;
+        ca[2 * k + 1] |= ad1;
+        cr[2 * k] |= rm0;
+        cr[2 * k + 1] |= rm1;
+      }
+    }
+    cnt = wave_sum(cnt);
+    const uint32_t na = cnt & 0xffffu, nr = cnt >> 16;
+    ta += (i64)na;
+    tr += (i64)nr;
+    if (FULL && lane == 0) {
+      if (na) atomicAdd(&a.row_added[r], (int32_t)na);
+      if (nr) atomicAdd(&a.row_removed[r], (int32_t)nr);
+    }
+  }
+}
+
+template <bool FULL>
+__global__ __launch_bounds__(TPB) void k_diff_rows(DiffArgs a) {
+  __shared__ u64 s_col[FULL ? 2 * DIFF_CW : 2];
+  __shared__ i64 s_tot[2 * (TPB / 64)];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  u64 ca[2 * DIFF_K], cr[2 * DIFF_K];
+#pragma unroll
+  for (int k = 0; k < 2 * DIFF_K; ++k) ca[k] = cr[k] = 0ull;
+  i64 ta = 0, tr = 0;
+  if (FULL) {
+    for (int w = threadIdx.x; w < 2 * DIFF_CW; w += TPB) s_col[w] = 0ull;
+    __syncthreads();
+  }
+  // the waves' column words of chunk c: OR-ed in LDS, one global atomic per
+  // non-zero word (every branch around it is block-uniform)
+  auto flush = [&](i64 c) {
+#pragma unroll
+    for (int k = 0; k < 2 * DIFF_K; ++k) {
+      const int w = 128 * (k >> 1) + lane * 2 + (k & 1);
+      if (ca[k]) atomicOr(&s_col[w], ca[k]);
+      if (cr[k]) atomicOr(&s_col[DIFF_CW + w], cr[k]);
+      ca[k] = cr[k] = 0ull;
+    }
+    __syncthreads();
+    for (int w = threadIdx.x; w < 2 * DIFF_CW; w += TPB) {
+      const u64 v = s_col[w];
+      if (v) {
+        const bool rem = w >= DIFF_CW;
+        const i64 gw = c * a.cw + (rem ? w - DIFF_CW : w);
+        if (gw < a.W) atomicOr(&(rem ? a.col_removed : a.col_added)[gw], v);
+        s_col[w] = 0ull;
+      }
+    }
+    __syncthreads();
+  };
+  i64 cur = -1;
+  for (i64 t = blockIdx.x; t < a.items; t += gridDim.x) {
+    const i64 c = t / a.nrg, g = t - c * a.nrg;
+    if (FULL && c != cur) {
+      if (cur >= 0) flush(cur);
+      cur = c;
+    }
+    diff_item<FULL>(a, c * a.cw, min(a.W, (c + 1) * a.cw), g * DIFF_ROWS, ca, cr, ta, tr);
+  }
+  if (FULL && cur >= 0) flush(cur);
+  if (lane == 0) {
+    s_tot[wid] = ta;
+    s_tot[TPB / 64 + wid] = tr;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    i64 s = 0;
+    for (int w = 0; w < TPB / 64; ++w) s += s_tot[threadIdx.x * (TPB / 64) + w];
+    if (s) atomicAdd(&a.totals[threadIdx.x], (u64)s);
+  }
+}
+
+// The pairs of one kind (0 added, 1 removed) of rows [0, rows) of the two
+// pointers, as (row0 + r, j) int32 pairs ascending by row, then column.  One
+// wave per row: the lanes take 64 consecutive words, a wave exclusive scan of
+// their popcounts gives each lane its slot behind the row's offset (off: the
+// exclusive scan of the rows' counts, rows + 1 entries), and a lane writes
+// its set bits lowest first -- the order is by construction.  A row without
+// a pair is not read.  No pair is written at or past off[r + 1] or cap.
+struct DiffEmitArgs {
+  const u64* A;
+  i64 ldA;
+  const u64* B;
+  i64 ldB;
+  i64 rows, W, n;
+  int kind;
+  i64 row0;
+  const i64* off;
+  i64 cap;
+  int32_t* pairs;
+};
+
+__global__ __launch_bounds__(TPB) void k_diff_emit(DiffEmitArgs a) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  for (i64 r = (i64)blockIdx.x * (TPB / 64) + wid; r < a.rows; r += (i64)gridDim.x * (TPB / 64)) {
+    const i64 beg = a.off[r], end = min(a.off[r + 1], a.cap);
+    if (beg >= end) continue;   // (wave-uniform)
+    const u64* pa = a.A + r * a.ldA;
+    const u64* pb = a.B + r * a.ldB;
+    const int32_t i = (int32_t)(a.row0 + r);
+    i64 pos = beg;
+    for (i64 wb = 0; wb < a.W; wb += 64) {
+      const i64 w = wb + lane;
+      u64 x = 0;
+      if (w < a.W) {
+        const u64 va = pa[w], vb = pb[w];
+        x = (a.kind ? va & ~vb : vb & ~va) & valid_mask(w, a.n);
+      }
+      int tot;
+      i64 p = pos + wave_excl_scan((int)__popcll(x), tot);
+      while (x) {
+        const int b = __ffsll((long long)x) - 1;
+        x &= x - 1;
+        if (p < end) *reinterpret_cast<int2*>(a.pairs + 2 * p) = make_int2(i, (int)(w * 64 + b));
+        ++p;
+      }
+      pos += tot;
+    }
+  }
+}
+
 }  // namespace kano

@@ -619,6 +619,66 @@ class DeviceBuild:
                   "kano_policy_impact")
         return out.astype(bool)
 
+    # -- matrix_diff (kano_diff / kano_diff_pairs / kano_copy_matrix) -----
+    DIFF_KINDS = {"added": 0, "removed": 1}
+
+    def diff(self, other: "DeviceBuild", rows: bool = True, cols: bool = True) -> dict:
+        """What ``other`` (B) holds and this context (A) does not, and the
+        reverse, over the rows both hold: ``added`` / ``removed`` (int),
+        ``row_added`` / ``row_removed`` (int32 per local row) and
+        ``col_added`` / ``col_removed`` (u64 words: columns that gained / lost
+        a source).  ``rows=False`` / ``cols=False`` leave those arrays out
+        (None); without both only the totals are computed."""
+        info = self.info()
+        rl, W = max(info["ROW1"] - info["ROW0"], 0), info["W"]
+        tot = np.zeros(2, dtype=np.int64)
+        ra = np.zeros(rl, dtype=np.int32) if rows else None
+        rr = np.zeros(rl, dtype=np.int32) if rows else None
+        ca = np.zeros(W, dtype=np.uint64) if cols else None
+        cr = np.zeros(W, dtype=np.uint64) if cols else None
+        # (errors are reported on the second context)
+        nat.check(other.ctx, self.lib.kano_diff(self.ctx, other.ctx, _ptr(tot), _ptr(ra), _ptr(rr),
+                                                _ptr(ca), _ptr(cr)), "kano_diff")
+        return dict(added=int(tot[0]), removed=int(tot[1]), row_added=ra, row_removed=rr,
+                    col_added=ca, col_removed=cr)
+
+    def diff_count(self, other: "DeviceBuild", kind, r0: int, nrows: int) -> int:
+        """The number of pairs ``diff_pairs`` would return."""
+        cnt = c_int64(0)
+        k = self.DIFF_KINDS.get(kind, kind)
+        nat.check(other.ctx, self.lib.kano_diff_pairs(self.ctx, other.ctx, int(k), int(r0),
+                                                      int(nrows), 0, byref(cnt), None),
+                  "kano_diff_pairs")
+        return int(cnt.value)
+
+    def diff_pairs(self, other: "DeviceBuild", kind, r0: int, nrows: int,
+                   limit: int = 1_000_000) -> np.ndarray:
+        """The (i, j) pairs of one kind ("added": in ``other`` only, "removed":
+        in this context only; or 0 / 1) in rows [r0, r0 + nrows), int32 (T, 2),
+        ascending by i then j.  More than ``limit`` pairs raise OverflowError."""
+        count = self.diff_count(other, kind, r0, nrows)
+        if count > int(limit):
+            raise OverflowError(f"{count} pairs exceed the limit of {int(limit)}")
+        out = np.empty((count, 2), dtype=np.int32)
+        if count:
+            cnt = c_int64(0)
+            k = self.DIFF_KINDS.get(kind, kind)
+            nat.check(other.ctx, self.lib.kano_diff_pairs(self.ctx, other.ctx, int(k), int(r0),
+                                                          int(nrows), count, byref(cnt),
+                                                          _ptr(out)), "kano_diff_pairs")
+        return out
+
+    def copy_from(self, src: "DeviceBuild") -> None:
+        """This context's rows := src's rows, on the device (kano_copy_matrix)."""
+        self._chk(self.lib.kano_copy_matrix(src.ctx, self.ctx), "kano_copy_matrix")
+
+    def diff_time(self) -> float:
+        """The last diff's device time (ms) with this context as ``other``
+        (KANO_TUNE=timing=1; kano_diff_time)."""
+        ms = ctypes.c_float(0.0)
+        self._chk(self.lib.kano_diff_time(self.ctx, byref(ms)), "kano_diff_time")
+        return float(ms.value)
+
     def rows_timing(self, reset: bool = False) -> dict:
         """k_rows launch times (HIP events) since the last reset: sum, count,
         min, max (ms); waits for the context's work."""

@@ -7,7 +7,7 @@ Reference: kano_py/kano/algorithm.py:4-100.
 """
 from __future__ import annotations
 
-from typing import DefaultDict, Dict, List, Tuple
+from typing import DefaultDict, Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -339,6 +339,70 @@ def policy_redundant(matrix: ReachabilityMatrix, policies: List[Policy],
         ess = impact_from_lists(n_lists, nbits, soff, flat, aw, device=_engine(matrix).device,
                                 flags_only=True)
     return np.flatnonzero(~ess).tolist()
+
+
+# ---------------------------------------------------------------------------
+# What a change adds and removes.  Not part of kano_py's algorithm.py.  For
+# two matrices over the same pods (and, for row shards, the same rows),
+#   added(i, j) = after[i, j] and not before[i, j]
+#   removed(i, j) = before[i, j] and not after[i, j]
+# computed on the device in one pass over both (kano_diff): before and after
+# an incremental update (ReachabilityMatrix.snapshot), a matrix against its
+# two_hop / closure, kano's reading against kubesv's, a loaded file against
+# today's build.
+
+class MatrixDiff(NamedTuple):
+    added: int                 # pairs reachable in `after` only
+    removed: int               # pairs reachable in `before` only
+    row_added: np.ndarray      # int64, one per held row: the source's gained pairs
+    row_removed: np.ndarray
+    col_added: List[int]       # ascending destinations that gained at least one source
+    col_removed: List[int]
+
+    @property
+    def equal(self) -> bool:
+        return self.added == 0 and self.removed == 0
+
+
+def _diff_engines(before: ReachabilityMatrix, after: ReachabilityMatrix):
+    a, b = _engine(before, whole=False), _engine(after, whole=False)
+    if before.container_size != after.container_size:
+        raise ValueError(f"matrices of {before.container_size} and {after.container_size} "
+                         "containers cannot be compared")
+    if type(a) is not type(b) or getattr(a, "device", 0) != getattr(b, "device", 0):
+        raise ValueError("matrix_diff needs both matrices on the same device(s)")
+    if getattr(a, "row_span", None) != getattr(b, "row_span", None):
+        raise ValueError(f"the matrices hold different rows: {a.row_span} and {b.row_span}")
+    return a, b
+
+
+def matrix_diff(before: ReachabilityMatrix, after: ReachabilityMatrix) -> MatrixDiff:
+    """The pairs `after` holds and `before` does not, and the reverse: totals,
+    per-row counts and the columns touched (see MatrixDiff)."""
+    a, b = _diff_engines(before, after)
+    n = before.container_size
+    d = a.diff(b)
+    return MatrixDiff(d["added"], d["removed"], d["row_added"].astype(np.int64),
+                      d["row_removed"].astype(np.int64),
+                      set_bit_indices(d["col_added"], n).tolist(),
+                      set_bit_indices(d["col_removed"], n).tolist())
+
+
+def matrix_diff_pairs(before: ReachabilityMatrix, after: ReachabilityMatrix,
+                      kind: str = "added", limit: int = 1_000_000,
+                      rows: Optional[Tuple[int, int]] = None) -> np.ndarray:
+    """The (i, j) pairs of one kind ("added" or "removed") as an int32 (T, 2)
+    array, ascending by i then j; ``rows`` = (r0, r1) restricts the sources
+    (default: every held row).  More than ``limit`` pairs raise OverflowError
+    naming their number: narrow ``rows`` or raise the limit."""
+    if kind not in ("added", "removed"):
+        raise ValueError(f"kind must be 'added' or 'removed', not {kind!r}")
+    a, b = _diff_engines(before, after)
+    span = getattr(a, "row_span", None) or (0, before.container_size)
+    r0, r1 = span if rows is None else (int(rows[0]), int(rows[1]))
+    if not span[0] <= r0 <= r1 <= span[1]:
+        raise ValueError(f"rows [{r0}, {r1}) outside the held rows [{span[0]}, {span[1]})")
+    return a.diff_pairs(b, kind, r0, r1 - r0, limit=limit)
 
 
 # ---------------------------------------------------------------------------

@@ -695,6 +695,32 @@ class ReachabilityMatrix:
             del self._eids[k]
         self._lists = None
 
+    # ---- snapshots (not in kano_py) ---------------------------------------
+    def snapshot(self) -> "ReachabilityMatrix":
+        """A new matrix on the same device(s) holding a copy of the rows as
+        they stand (a device-to-device copy): no policies, so queries on the
+        rows work and incremental updates do not.  With the in-place updates
+        above this gives "snapshot, change, kano.algorithm.matrix_diff"."""
+        from ._engine import DeviceBuild
+        from .multi import MultiBuild
+        src = self._engine
+        n = self.container_size
+        out = ReachabilityMatrix.__new__(ReachabilityMatrix)
+        out.container_size = n
+        out._engine = (MultiBuild.empty(n, src.G, devices=src.devices)
+                       if isinstance(src, MultiBuild)
+                       else DeviceBuild.empty(n, device=src.device, rows=src.row_span))
+        out._containers = None
+        out._policies = None
+        out._ncontainers = n
+        out._lists = None
+        try:
+            out._engine.copy_from(src)
+        except BaseException:
+            out._engine.close()
+            raise
+        return out
+
     # ---- on-disk / tooling format (SURVEY.md §8(f) rank 4) -------------
     # Not in kano_py: its rows are bitarrays (model.py:136-139), and this
     # format is their bytes.  File: b"KANOMAT1", then n, r0, r1, row_bytes as

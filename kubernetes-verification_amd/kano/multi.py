@@ -449,6 +449,53 @@ class MultiBuild:
         keys = ("steps", "steps_run", "mfma_steps", "row_classes", "col_classes", "identity")
         return {k: int(v) for k, v in zip(keys, info)}
 
+    # -- matrix_diff: member against member -------------------------------------
+    def _same_shards(self, other, what: str) -> None:
+        if (not isinstance(other, MultiBuild) or other.G != self.G or
+                other.devices != self.devices or other.bounds != self.bounds):
+            raise ValueError(f"{what} needs a group over the same devices and row shards")
+
+    def diff(self, other: "MultiBuild", rows: bool = True, cols: bool = True) -> dict:
+        """DeviceBuild.diff over the row-sharded matrices: the members' totals
+        summed, row counts concatenated, column words OR-ed."""
+        self._same_shards(other, "diff")
+        parts = [m.diff(o, rows=rows, cols=cols) for m, o in zip(self.members, other.members)]
+        out = dict(added=sum(p["added"] for p in parts), removed=sum(p["removed"] for p in parts))
+        for k in ("row_added", "row_removed"):
+            out[k] = np.concatenate([p[k] for p in parts]) if rows else None
+        for k in ("col_added", "col_removed"):
+            out[k] = np.bitwise_or.reduce([p[k] for p in parts]) if cols else None
+        return out
+
+    def _diff_ranges(self, r0: int, nrows: int):
+        for r, (a, b) in enumerate(self.bounds):
+            lo, hi = max(a, r0), min(b, r0 + nrows)
+            if lo < hi:
+                yield r, lo, hi - lo
+
+    def diff_count(self, other: "MultiBuild", kind, r0: int, nrows: int) -> int:
+        self._same_shards(other, "diff_pairs")
+        if nrows < 0 or r0 < 0 or r0 + nrows > self.n:
+            raise ValueError("rows out of range")
+        return sum(self.members[r].diff_count(other.members[r], kind, lo, k)
+                   for r, lo, k in self._diff_ranges(int(r0), int(nrows)))
+
+    def diff_pairs(self, other: "MultiBuild", kind, r0: int, nrows: int,
+                   limit: int = 1_000_000) -> np.ndarray:
+        """The members' pairs in rank order (= row order)."""
+        count = self.diff_count(other, kind, r0, nrows)
+        if count > int(limit):
+            raise OverflowError(f"{count} pairs exceed the limit of {int(limit)}")
+        parts = [self.members[r].diff_pairs(other.members[r], kind, lo, k, limit=count)
+                 for r, lo, k in self._diff_ranges(int(r0), int(nrows))]
+        return (np.concatenate(parts).reshape(-1, 2) if parts
+                else np.zeros((0, 2), dtype=np.int32))
+
+    def copy_from(self, src: "MultiBuild") -> None:
+        self._same_shards(src, "copy_from")
+        for m, s in zip(self.members, src.members):
+            m.copy_from(s)
+
     # -- measurement ------------------------------------------------------------
     def exchange_timing(self, enable: Optional[bool] = None, reset: bool = False) -> dict:
         """The verify exchange's time on member 0's stream (HIP events around
