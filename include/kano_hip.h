@@ -256,6 +256,41 @@ int kano_copy_matrix(kano_ctx* src, kano_ctx* dst);
  * kernel without the copies, in ms; recorded under KANO_TUNE=timing=1, else 0. */
 int kano_diff_time(kano_ctx* ctx, float* ms);
 
+/* group_reachability: the matrix's quotient by two pod labellings.  gsrc[i] is
+ * the source group of pod i and gdst[j] the destination group of pod j, both
+ * int32 over all n pods (the same labelling or two different ones); for the
+ * rows r0..r1 this context holds,
+ *   counts[g][h]     = #{(i, j) : r0 <= i < r1, 0 <= j < n, M[i,j] = 1,
+ *                        gsrc[i] = g, gdst[j] = h}        (int64, Gs x Gd, row-major)
+ *   row_counts[i][h] = #{j : M[i,j] = 1, gdst[j] = h}    (int32, rows_local x Gd)
+ * A negative id leaves that pod out: a row with gsrc[i] < 0 adds to no counts
+ * entry (its row_counts are still computed), a column with gdst[j] < 0 is
+ * counted nowhere.  Bits at positions >= n of a row's last word (kano_put_rows
+ * copies them unmasked) belong to no group.  Exact integers.  row_counts may
+ * be NULL.  Works on every matrix a context holds (built, edited, updated,
+ * loaded, path, edge, row shard): the matrix is present (as for
+ * kano_get_rows), pending work is waited for, and the passes over the
+ * resident rows run on the context's stream in device buffers that are the
+ * call's own.  n == 0 or no local rows gives zeros.  The counts of row shards
+ * add up, their row_counts concatenate.
+ * -EINVAL: a NULL context, gsrc, gdst or counts, Gs <= 0 or Gd <= 0;
+ * -ERANGE: an id >= its group count (both arrays are scanned on the host);
+ * -ENOTSUP: Gs * Gd > 134,217,728 (2^27 cells, 1 GiB of counts: ask for
+ * row_counts with fewer source groups instead); -ENOMEM (with a message): a
+ * device buffer could not be allocated -- the masks (at most 1 GiB a pass),
+ * Gs * Gd * 8 bytes, rows_local * Gd * 4 bytes.  The context stays usable
+ * after every error.  The matrix, the class tables and every stored check
+ * result (column words, crosscheck words, shadow and conflict pairs, impact)
+ * are unchanged; a call between pipelined kano_verify steps leaves the next
+ * step's results unchanged. */
+int kano_group_counts(kano_ctx* ctx, const int32_t* gsrc /* n */, int32_t Gs,
+                      const int32_t* gdst /* n */, int32_t Gd,
+                      int64_t* counts /* Gs*Gd, row-major */,
+                      int32_t* row_counts /* rows_local*Gd, or NULL */);
+/* The last kano_group_counts' device time, fills and kernels without the
+ * copies, in ms; recorded under KANO_TUNE=timing=1, else 0. */
+int kano_group_counts_time(kano_ctx* ctx, float* ms);
+
 /* The whole verification pass in one call (the sequence kano_py's
  * sample/example.py and tests/test_basic.py run: build_matrix, then
  * all_reachable, all_isolated, user_crosscheck, system_isolation and

@@ -165,6 +165,9 @@ struct kano_ctx {
                              // (n > 524k) take, forced at small n
   int impact_form = 0;       // impf=1/2: policy_impact's list / row form forced (0: by density)
   int diff_grid = 0;         // dgrid=K: at most K blocks for k_diff_rows (0: every resident block)
+  int group_grid = 0;        // ggrid=K: at most K blocks for k_group_rows (0: every resident block)
+  int group_batches = 0;     // gbatch=K: at most K batches of 64 destination groups in one
+                             // pass of kano_group_counts (0: by the mask budget)
   int shadow_r = 0;          // shr=1/2/4/8: k_shadow_test1s's 256-pair rounds per block (0: auto)
   int shg_sub_lds = 1;       // shgsub=0: forces k_shg_sub's word-by-word row compare (the
                              // form rows wider than 64 KB of LDS take)
@@ -260,6 +263,9 @@ struct kano_ctx {
   // written (the offsets and pairs of kano_diff_pairs are temporaries)
   DBuf diff_buf;
   float diff_ms = 0.f;        // timing=1: the last kano_diff's fill + kernel (kano_diff_time)
+  // group_reachability (kano_group_counts): its device buffers are the
+  // call's own; only the time stays
+  float group_ms = 0.f;       // timing=1: the last call's fills + kernels (kano_group_counts_time)
   // policy_shadow count-only (kano_verify with shadow_cap < 0): the grouped
   // count (k_shg_*) instead of the pair-by-pair flags
   bool vs_count_only = false;
@@ -425,6 +431,18 @@ int diff_rows_launch(kano_ctx* ctx, const u64* A, i64 ldA, const u64* B, i64 ldB
 int diff_offsets_launch(kano_ctx* ctx, const int32_t* cnt, i64 rows, i64* tmp, i64* off);
 int diff_emit_launch(kano_ctx* ctx, const u64* A, i64 ldA, const u64* B, i64 ldB, i64 rows,
                      int kind, i64 row0, const i64* off, i64 cap, int32_t* pairs);
+
+// group_reachability's launches (kano_hip.hip, next to the kernels; the entry
+// point is kano_ext.hip's)
+struct GroupRun {
+  int32_t group;            // source group, -1: rows that only want row_counts
+  int32_t first, len;       // order[first .. first + len)
+};
+i64 group_chunks(const kano_ctx* ctx);              // column chunks of a row
+i64 group_run_rows(kano_ctx* ctx, i64 sel, i64 nbp, bool rows);   // rows of a run
+int group_masks_launch(kano_ctx* ctx, const int32_t* gd, i64 b0, i64 nbp, u64* maskT);
+int group_rows_launch(kano_ctx* ctx, const u64* maskT, i64 b0, i64 nbp, const int32_t* order,
+                      const GroupRun* runs, i64 nruns, i64 Gd, u64* counts, int32_t* row_counts);
 
 template <typename T>
 T* P_(DBuf& b) {

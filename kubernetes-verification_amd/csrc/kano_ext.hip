@@ -910,3 +910,142 @@ int kano_diff_time(kano_ctx* ctx, float* ms) {
 }
 
 }  // extern "C"
+
+// ===========================================================================
+// group_reachability: the matrix's quotient by two pod labellings
+// (k_group_masks / k_group_rows, kano_kernels.hpp; launched through
+// kano_hip.hip's helpers).
+// ===========================================================================
+namespace {
+
+constexpr i64 GROUP_MAX_CELLS = 1ll << 27;     // Gs * Gd of one call (1 GiB of counts)
+constexpr i64 GROUP_MASK_BUDGET = 1ll << 30;   // bytes of transposed masks of one pass
+
+// the local rows in source-group order and their runs of at most run_len
+// rows; the rows left out of counts follow as runs of group -1 when with_out
+void group_runs(const int32_t* gs, i64 r0, i64 rl, i64 Gs, bool with_out, i64 run_len,
+                std::vector<int32_t>& order, std::vector<GroupRun>& runs) {
+  order.clear();
+  runs.clear();
+  order.reserve((size_t)rl);
+  auto key = [&](i64 r) -> i64 { return gs[r0 + r] < 0 ? Gs : gs[r0 + r]; };
+  if (Gs <= (1ll << 22)) {   // a counting sort (stable: rows ascending in a group)
+    std::vector<i64> pos((size_t)Gs + 2, 0);
+    for (i64 r = 0; r < rl; ++r) ++pos[key(r) + 1];
+    for (i64 g = 0; g <= Gs; ++g) pos[g + 1] += pos[g];
+    order.resize((size_t)rl);
+    for (i64 r = 0; r < rl; ++r) order[pos[key(r)]++] = (int32_t)r;
+  } else {
+    for (i64 r = 0; r < rl; ++r) order.push_back((int32_t)r);
+    std::stable_sort(order.begin(), order.end(),
+                     [&](int32_t x, int32_t y) { return key(x) < key(y); });
+  }
+  if (!with_out)
+    while (!order.empty() && key(order.back()) == Gs) order.pop_back();
+  const i64 m = (i64)order.size();
+  for (i64 p = 0; p < m;) {
+    const i64 k = key(order[p]);
+    i64 q = p;
+    while (q < m && q - p < run_len && key(order[q]) == k) ++q;
+    runs.push_back(GroupRun{k == Gs ? -1 : (int32_t)k, (int32_t)p, (int32_t)(q - p)});
+    p = q;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int kano_group_counts(kano_ctx* ctx, const int32_t* gsrc, int32_t Gs, const int32_t* gdst,
+                      int32_t Gd, int64_t* counts, int32_t* row_counts) {
+  if (!ctx) return -EINVAL;
+  if (!gsrc || !gdst || !counts)
+    return fail(ctx, -EINVAL, "kano_group_counts: gsrc, gdst or counts is NULL");
+  if (Gs <= 0 || Gd <= 0) return fail(ctx, -EINVAL, "kano_group_counts: Gs and Gd must be > 0");
+  if ((i64)Gs * Gd > GROUP_MAX_CELLS)
+    return fail(ctx, -ENOTSUP, "kano_group_counts: Gs * Gd = " + std::to_string((i64)Gs * Gd) +
+                                   " beyond " + std::to_string(GROUP_MAX_CELLS) +
+                                   " (ask for row_counts with fewer source groups)");
+  KTRY(ensure_matrix(ctx));
+  const i64 n = ctx->n, W = ctx->W, rl = std::max<i64>(0, rows_local(ctx));
+  for (i64 i = 0; i < n; ++i)
+    if (gsrc[i] >= Gs || gdst[i] >= Gd)
+      return fail(ctx, -ERANGE, "kano_group_counts: pod " + std::to_string(i) +
+                                    " has a group id at or past its group count");
+  const size_t cells = (size_t)Gs * (size_t)Gd, rcells = (size_t)rl * (size_t)Gd;
+  std::memset(counts, 0, sizeof(int64_t) * cells);
+  if (row_counts && rcells) std::memset(row_counts, 0, sizeof(int32_t) * rcells);
+  KTRY(sync(ctx));
+  if (n == 0 || W == 0 || rl == 0) return 0;
+
+  // passes of nbp batches of 64 destination groups
+  const i64 nb = ((i64)Gd + 63) / 64;
+  i64 nbp = std::max<i64>(1, GROUP_MASK_BUDGET / (512 * W));
+  nbp = std::min(nbp, std::max<i64>(1, (i64)0x7fffffff / W));
+  if (ctx->group_batches > 0) nbp = std::min<i64>(nbp, ctx->group_batches);
+  nbp = std::min(nbp, nb);
+  std::vector<int32_t> order;
+  std::vector<GroupRun> runs;
+  group_runs(gsrc, ctx->r0, rl, Gs, row_counts != nullptr,
+             group_run_rows(ctx, rl, nbp, row_counts != nullptr), order, runs);
+  const i64 nruns = (i64)runs.size();
+  if (nruns == 0) return 0;   // every source id negative, no row counts wanted
+
+  // the call's own buffers
+  DBuf in, masks, out, rows;
+  auto run = [&]() -> int {
+    const size_t b_gd = sizeof(int32_t) * (size_t)n, b_ord = sizeof(int32_t) * order.size(),
+                 b_run = sizeof(GroupRun) * runs.size();
+    KTRY(dalloc(ctx, in, b_gd + b_ord + b_run));
+    KTRY(dalloc(ctx, masks, sizeof(u64) * 64 * (size_t)nbp * (size_t)W));
+    KTRY(dalloc(ctx, out, sizeof(u64) * cells));
+    if (row_counts) KTRY(dalloc(ctx, rows, sizeof(int32_t) * rcells));
+    char* ip = static_cast<char*>(in.p);
+    KCHK(hipMemcpyAsync(ip, gdst, b_gd, hipMemcpyHostToDevice, ctx->stream));
+    KCHK(hipMemcpyAsync(ip + b_gd, order.data(), b_ord, hipMemcpyHostToDevice, ctx->stream));
+    KCHK(hipMemcpyAsync(ip + b_gd + b_ord, runs.data(), b_run, hipMemcpyHostToDevice,
+                        ctx->stream));
+    // timing=1: the call's device time (the fills and the kernels, no copy)
+    hipEvent_t tev[2] = {nullptr, nullptr};
+    if (ctx->stage_timing) {
+      KCHK(hipEventCreate(&tev[0]));
+      KCHK(hipEventCreate(&tev[1]));
+      KCHK(hipEventRecord(tev[0], ctx->stream));
+    }
+    KCHK(hipMemsetAsync(out.p, 0, sizeof(u64) * cells, ctx->stream));
+    if (row_counts) KCHK(hipMemsetAsync(rows.p, 0, sizeof(int32_t) * rcells, ctx->stream));
+    const int32_t* gd_d = reinterpret_cast<const int32_t*>(ip);
+    const int32_t* ord_d = reinterpret_cast<const int32_t*>(ip + b_gd);
+    const GroupRun* run_d = reinterpret_cast<const GroupRun*>(ip + b_gd + b_ord);
+    for (i64 b0 = 0; b0 < nb; b0 += nbp) {
+      const i64 k = std::min(nbp, nb - b0);
+      KTRY(group_masks_launch(ctx, gd_d, b0, k, P_<u64>(masks)));
+      KTRY(group_rows_launch(ctx, P_<u64>(masks), b0, k, ord_d, run_d, nruns, Gd, P_<u64>(out),
+                             row_counts ? P_<int32_t>(rows) : nullptr));
+    }
+    if (tev[0]) {
+      KCHK(hipEventRecord(tev[1], ctx->stream));
+      KCHK(hipEventSynchronize(tev[1]));
+      (void)hipEventElapsedTime(&ctx->group_ms, tev[0], tev[1]);
+      (void)hipEventDestroy(tev[0]);
+      (void)hipEventDestroy(tev[1]);
+    }
+    KCHK(hipMemcpyAsync(counts, out.p, sizeof(u64) * cells, hipMemcpyDeviceToHost, ctx->stream));
+    if (row_counts)
+      KCHK(hipMemcpyAsync(row_counts, rows.p, sizeof(int32_t) * rcells, hipMemcpyDeviceToHost,
+                          ctx->stream));
+    return sync(ctx);
+  };
+  const int rc = run();
+  if (rc) (void)hipStreamSynchronize(ctx->stream);   // nothing in flight on the temporaries
+  for (DBuf* b : {&in, &masks, &out, &rows}) dfree(*b);
+  return rc;
+}
+
+int kano_group_counts_time(kano_ctx* ctx, float* ms) {
+  if (!ctx || !ms) return -EINVAL;
+  *ms = ctx->group_ms;
+  return 0;
+}
+
+}  // extern "C"

@@ -2153,6 +2153,89 @@ int diff_emit_launch(kano_ctx* ctx, const u64* A, i64 ldA, const u64* B, i64 ldB
   return 0;
 }
 
+// group_reachability's launches (k_group_masks, k_group_rows:
+// kano_kernels.hpp) for kano_group_counts in kano_ext.hip, on ctx's stream.
+// W is split into equal chunks of at most GROUP_CW words, whole 64-word
+// blocks each (as diff_rows_launch: no narrow last chunk).
+static i64 group_chunk_words(i64 W) {
+  const i64 nch = (W + GROUP_CW - 1) / GROUP_CW;
+  return nch ? std::min<i64>(GROUP_CW, ((W + nch - 1) / nch + 63) / 64 * 64) : GROUP_CW;
+}
+
+i64 group_chunks(const kano_ctx* ctx) {
+  const i64 cw = group_chunk_words(ctx->W);
+  return (ctx->W + cw - 1) / cw;
+}
+
+static i64 group_blocks(kano_ctx* ctx, bool rows) {
+  static int per_cu[2] = {0, 0};
+  if (!per_cu[rows]) {
+    int nb = 0;
+    const hipError_t e =
+        rows ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_group_rows<true>, TPB, 0)
+             : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_group_rows<false>, TPB, 0);
+    per_cu[rows] = (e == hipSuccess && nb > 0) ? std::min(nb, 8) : 4;
+  }
+  const i64 cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
+  i64 blocks = cus * per_cu[rows];
+  if (ctx->group_grid > 0) blocks = std::min<i64>(blocks, ctx->group_grid);
+  return blocks;
+}
+
+// the rows of a run for `sel` rows in passes of nbp batches: about four items
+// a resident wave (a run ends in up to 64 atomics on its source group's row of
+// counts, so runs are as long as the load balance allows), whole row groups
+i64 group_run_rows(kano_ctx* ctx, i64 sel, i64 nbp, bool rows) {
+  const i64 target = 4 * group_blocks(ctx, rows) * (TPB / 64);
+  const i64 units = std::max<i64>(1, sel) * std::max<i64>(1, group_chunks(ctx) * nbp);
+  const i64 len = (units + target - 1) / target;
+  return std::min<i64>(4096, (len + GROUP_R - 1) / GROUP_R * GROUP_R);
+}
+
+// maskT[bb][w][l] for the batches b0 .. b0 + nbp of gd (device, n entries)
+int group_masks_launch(kano_ctx* ctx, const int32_t* gd, i64 b0, i64 nbp, u64* maskT) {
+  const i64 waves = nbp * ctx->W;
+  if (waves <= 0) return 0;
+  if (waves > (i64)0x7fffffff) return fail(ctx, -ENOTSUP, "kano_group_counts: mask pass too large");
+  hipLaunchKernelGGL(k_group_masks, dim3(nblk(waves, TPB / 64)), dim3(TPB), 0, ctx->stream, gd,
+                     ctx->n, ctx->W, b0, nbp, maskT);
+  KLAUNCH();
+  return 0;
+}
+
+// one pass: the batches b0 .. b0 + nbp over every run.  counts and
+// row_counts (NULL: not asked for) accumulate; they are zero before the
+// first pass.
+int group_rows_launch(kano_ctx* ctx, const u64* maskT, i64 b0, i64 nbp, const int32_t* order,
+                      const GroupRun* runs, i64 nruns, i64 Gd, u64* counts, int32_t* row_counts) {
+  const i64 W = ctx->W;
+  if (nruns <= 0 || W <= 0 || nbp <= 0) return 0;
+  static_assert(sizeof(GroupRun) == 3 * sizeof(int32_t), "runs are int32 triples");
+  GroupRowsArgs a{};
+  a.M = P_<u64>(ctx->M);
+  a.ldM = ctx->ldM;
+  a.W = W;
+  a.maskT = maskT;
+  a.order = order;
+  a.runs = reinterpret_cast<const int32_t*>(runs);
+  a.nruns = nruns;
+  a.cw = group_chunk_words(W);
+  a.nch = (W + a.cw - 1) / a.cw;
+  a.items = nbp * a.nch * nruns;
+  a.b0 = b0;
+  a.Gd = Gd;
+  a.counts = counts;
+  a.row_counts = row_counts;
+  // every block resident, its waves striding over the items
+  const bool rows = row_counts != nullptr;
+  const i64 blocks = std::min<i64>((a.items + TPB / 64 - 1) / (TPB / 64), group_blocks(ctx, rows));
+  const unsigned grid = (unsigned)std::max<i64>(1, blocks);
+  if (rows) hipLaunchKernelGGL((k_group_rows<true>), dim3(grid), dim3(TPB), 0, ctx->stream, a);
+  else hipLaunchKernelGGL((k_group_rows<false>), dim3(grid), dim3(TPB), 0, ctx->stream, a);
+  KLAUNCH();
+  return 0;
+}
+
 }  // namespace kano_eng
 
 using namespace kano_eng;
@@ -2221,6 +2304,8 @@ int kano_create(int device, kano_ctx** out) {
         if (k == "shgsub") ctx->shg_sub_lds = v;
         if (k == "impf" && v >= 0 && v <= 2) ctx->impact_form = v;
         if (k == "dgrid" && v >= 0) ctx->diff_grid = v;
+        if (k == "ggrid" && v >= 0) ctx->group_grid = v;
+        if (k == "gbatch" && v >= 0) ctx->group_batches = v;
         if (k == "shr" && (v == 1 || v == 2 || v == 4 || v == 8)) ctx->shadow_r = v;
         if (k == "rcu" && v >= 0 && v <= 28 && (v < 4 || v % 4 == 0)) ctx->rows_cu_off = v;
         if (k == "rcubytes" && v >= 0) ctx->rows_cu_bytes = (i64)v << 30;

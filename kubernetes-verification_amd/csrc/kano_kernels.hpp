@@ -3943,4 +3943,149 @@ __global__ __launch_bounds__(TPB) void k_diff_emit(DiffEmitArgs a) {
   }
 }
 
+// ===========================================================================
+// group_reachability: the quotient of the matrix by two pod labellings,
+//   counts[g][h]     = #{(i, j) : M[i,j] = 1, gs[i] = g, gd[j] = h}
+//   row_counts[i][h] = #{j : M[i,j] = 1, gd[j] = h}
+// Not part of kano_py; the host restatement is tests/test_groups.py's.
+//
+// k_group_masks turns the destination labelling into transposed masks for a
+// pass of nbp batches of 64 destination groups from batch b0 on:
+// maskT[bb][w][l] holds the bits j of word w with gd[j] == 64 (b0 + bb) + l.
+// One wave per (bb, w): lane l reads gd[64 w + l] (-1 at or past n, so the
+// row tails and the negative ids are in no mask), and 64 ballots hand lane k
+// the lanes whose id is its group.  A word none of whose ids lies in the
+// batch (block-contiguous labellings: most of them) takes no ballot.
+//
+// k_group_rows counts.  Lane l of a wave is destination group 64 (b0 + bb) +
+// l.  A wave's item is (batch, column chunk of cw words, run): a run is up to
+// the host's run length of rows of one source group (order: the local rows
+// sorted by source group; runs: (group, first, length), group -1 for rows
+// left out of counts that still want row_counts).  The wave walks its run
+// GROUP_R rows at a time; per 64 words of the chunk it loads one word a lane
+// and row (coalesced), and for every word position k at which any of the
+// rows holds a bit -- a ballot, so the loop is scalar and zero words cost
+// nothing beyond the load -- it loads the mask word of (w0 + k, lane) once
+// (the next position's while this one's is in use), reads the words k of the
+// rows that hold a bit there from lane k (a ballot per row: a row whose word
+// is zero takes a scalar branch and no vector instruction), and adds
+// popcount(x & mask) into one 32-bit register a row (a (row, chunk) holds at
+// most GROUP_CW * 64 bits).
+// The lane is the output column: there is no cross-lane reduction.  After a
+// row group each non-zero (row, lane) is one 32-bit atomicAdd into
+// row_counts (ROWS) and joins the lane's 64-bit run total; a run ends in one
+// 64-bit atomicAdd per non-zero lane.  The outputs are zero before the
+// launch; the pitch beyond W words is not read.
+// ===========================================================================
+constexpr int GROUP_R = 8;       // rows of a run that share one mask load
+constexpr int GROUP_CW = 256;    // words of a column chunk (a multiple of 64)
+static_assert(GROUP_CW % 64 == 0 && (i64)GROUP_CW * 64 <= 0x7fffffff, "chunk bits fit 32");
+
+__global__ __launch_bounds__(TPB) void k_group_masks(const int32_t* __restrict__ gd, i64 n, i64 W,
+                                                     i64 b0, i64 nbp, u64* __restrict__ maskT) {
+  const int lane = threadIdx.x & 63;
+  const i64 t = (i64)blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
+  if (t >= nbp * W) return;   // (wave-uniform)
+  const i64 bb = t / W, w = t - bb * W;
+  const i64 j = w * 64 + lane;
+  const i64 g = j < n ? (i64)gd[j] : -1;
+  const i64 rel = g < 0 ? -1 : g - 64 * (b0 + bb);
+  u64 mine = 0ull;
+  if (__any(rel >= 0 && rel < 64)) {
+#pragma unroll 8
+    for (int k = 0; k < 64; ++k) {
+      const u64 m = __ballot(rel == k);
+      if (lane == k) mine = m;
+    }
+  }
+  maskT[t * 64 + lane] = mine;
+}
+
+struct GroupRowsArgs {
+  const u64* M;             // the local rows
+  i64 ldM, W;
+  const u64* maskT;         // [nbp][W][64]
+  const int32_t* order;     // local row indices sorted by source group
+  const int32_t* runs;      // (group or -1, first, length) per run
+  i64 nruns, nch, cw;       // runs; column chunks; words of a chunk (a multiple of 64)
+  i64 items;                // nbp * nch * nruns
+  i64 b0;                   // the pass's first batch
+  i64 Gd;
+  u64* counts;              // Gs x Gd
+  int32_t* row_counts;      // rows_local x Gd (ROWS)
+};
+
+// word k of the wave's 64 loaded words (k wave-uniform)
+__device__ __forceinline__ u64 group_lane_word(u64 v, int k) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, k);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), k);
+  return ((u64)hi << 32) | lo;
+}
+
+template <bool ROWS>
+__global__ __launch_bounds__(TPB) void k_group_rows(GroupRowsArgs a) {
+  const int lane = threadIdx.x & 63;
+  const i64 nwv = (i64)gridDim.x * (TPB / 64);
+  const i64 per = a.nch * a.nruns;
+  for (i64 t = (i64)blockIdx.x * (TPB / 64) + (threadIdx.x >> 6); t < a.items; t += nwv) {
+    // batch-major, then chunk-major: the waves running together share a
+    // chunk's slice of one batch's masks (cw * 512 bytes)
+    const i64 bb = t / per, rem = t - bb * per, c = rem / a.nruns, run = rem - c * a.nruns;
+    const int32_t g = a.runs[3 * run], first = a.runs[3 * run + 1], len = a.runs[3 * run + 2];
+    const i64 h = 64 * (a.b0 + bb) + lane;
+    const bool live = h < a.Gd;
+    const u64* mk = a.maskT + bb * a.W * 64 + lane;
+    const i64 c0 = c * a.cw, cend = min(a.W, c0 + a.cw);
+    u64 total = 0ull;
+#pragma unroll 1
+    for (int32_t p = 0; p < len; p += GROUP_R) {
+      i64 row[GROUP_R];
+      uint32_t acc[GROUP_R];
+#pragma unroll
+      for (int r = 0; r < GROUP_R; ++r) {
+        row[r] = p + r < len ? (i64)a.order[first + p + r] : -1;
+        acc[r] = 0u;
+      }
+#pragma unroll 1
+      for (i64 w0 = c0; w0 < cend; w0 += 64) {
+        const bool in = w0 + lane < cend;
+        u64 v[GROUP_R], nzr[GROUP_R], nz = 0ull;
+#pragma unroll
+        for (int r = 0; r < GROUP_R; ++r)
+          v[r] = (in && row[r] >= 0) ? a.M[row[r] * a.ldM + w0 + lane] : 0ull;
+#pragma unroll
+        for (int r = 0; r < GROUP_R; ++r) {
+          nzr[r] = __ballot(v[r] != 0ull);   // the word positions at which row r holds a bit
+          nz |= nzr[r];
+        }
+        if (nz == 0ull) continue;
+        // one turn per word position holding a bit of any row (scalar); the
+        // next position's mask word is loaded before this one's is used, and
+        // a row whose word is zero takes no vector instruction
+        int k = __builtin_ctzll(nz);
+        u64 m = mk[(w0 + k) * 64];
+        for (;;) {
+          nz &= nz - 1;
+          const int kn = nz ? __builtin_ctzll(nz) : k;
+          const u64 mn = mk[(w0 + kn) * 64];
+#pragma unroll
+          for (int r = 0; r < GROUP_R; ++r)
+            if ((nzr[r] >> k) & 1ull) acc[r] += (uint32_t)__popcll(group_lane_word(v[r], k) & m);
+          if (nz == 0ull) break;
+          k = kn;
+          m = mn;
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < GROUP_R; ++r) {
+        if (acc[r] && live) {
+          total += acc[r];
+          if (ROWS) atomicAdd(&a.row_counts[row[r] * a.Gd + h], (int32_t)acc[r]);
+        }
+      }
+    }
+    if (g >= 0 && live && total) atomicAdd(&a.counts[(i64)g * a.Gd + h], total);
+  }
+}
+
 }  // namespace kano

@@ -679,6 +679,38 @@ class DeviceBuild:
         self._chk(self.lib.kano_diff_time(self.ctx, byref(ms)), "kano_diff_time")
         return float(ms.value)
 
+    # -- group_reachability (kano_group_counts) ----------------------------
+    def group_counts(self, gs, gd, Gs: Optional[int] = None, Gd: Optional[int] = None,
+                     rows: bool = False) -> dict:
+        """The matrix's quotient by a source and a destination labelling of
+        the pods (int32 ids over all n pods; a negative id leaves the pod
+        out): ``counts`` (int64, Gs x Gd) over the rows this context holds
+        and, with ``rows``, ``row_counts`` (int32, one row of Gd counts per
+        held row; else None).  ``Gs`` / ``Gd`` default to the largest id + 1
+        (at least 1)."""
+        info = self.info()
+        n, rl = info["N"], max(info["ROW1"] - info["ROW0"], 0)
+        gs = np.ascontiguousarray(gs, dtype=np.int32).reshape(-1)
+        gd = np.ascontiguousarray(gd, dtype=np.int32).reshape(-1)
+        if gs.shape[0] != n or gd.shape[0] != n:
+            raise ValueError("gs and gd must have one entry per pod")
+        if Gs is None:
+            Gs = max(int(gs.max()) + 1, 1) if n else 1
+        if Gd is None:
+            Gd = max(int(gd.max()) + 1, 1) if n else 1
+        Gs, Gd = int(Gs), int(Gd)
+        counts = np.zeros((max(Gs, 0), max(Gd, 0)), dtype=np.int64)
+        rc = np.zeros((rl, max(Gd, 0)), dtype=np.int32) if rows else None
+        self._chk(self.lib.kano_group_counts(self.ctx, _ptr(gs), Gs, _ptr(gd), Gd, _ptr(counts),
+                                             _ptr(rc)), "kano_group_counts")
+        return dict(counts=counts, row_counts=rc)
+
+    def group_counts_time(self) -> float:
+        """The last group_counts' device time (ms; KANO_TUNE=timing=1)."""
+        ms = ctypes.c_float(0.0)
+        self._chk(self.lib.kano_group_counts_time(self.ctx, byref(ms)), "kano_group_counts_time")
+        return float(ms.value)
+
     def rows_timing(self, reset: bool = False) -> dict:
         """k_rows launch times (HIP events) since the last reset: sum, count,
         min, max (ms); waits for the context's work."""

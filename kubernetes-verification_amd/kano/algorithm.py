@@ -72,6 +72,15 @@ def user_hashmap(containers: List[Container], label: str) -> Dict[str, BitArray]
     return out
 
 
+def group_keys(containers: List[Container], label: str) -> Tuple[list, np.ndarray]:
+    """user_hashmap's keys in its (first-appearance) order, a missing label
+    as "", and group_ids' dense ids into them: (keys, int32 gid)."""
+    keys: Dict = {}
+    for c in containers:
+        keys.setdefault(c.getValueOrDefault(label, ""), None)
+    return list(keys), group_ids(containers, label)
+
+
 def user_crosscheck(matrix: ReachabilityMatrix, containers: List[Container],
                     label: str) -> List[int]:
     """Containers j reachable from a container of another user group
@@ -403,6 +412,90 @@ def matrix_diff_pairs(before: ReachabilityMatrix, after: ReachabilityMatrix,
     if not span[0] <= r0 <= r1 <= span[1]:
         raise ValueError(f"rows [{r0}, {r1}) outside the held rows [{span[0]}, {span[1]})")
     return a.diff_pairs(b, kind, r0, r1 - r0, limit=limit)
+
+
+# ---------------------------------------------------------------------------
+# Who reaches whom, by group.  Not part of kano_py's algorithm.py.
+# user_crosscheck says which pods are reached from another group; these say
+# which group reaches which, through how many pod pairs and from which pods:
+#   counts[g][h] = #{(i, j) : M[i, j], group(i) = g, group(j) = h}
+# computed on the device from the matrix itself (kano_group_counts), so it
+# holds for built, updated, loaded, path and edge matrices alike.  A matrix
+# holding a row shard answers for its rows: the counts of the shards add up.
+
+class GroupReachability(NamedTuple):
+    src_keys: list             # label values in first-appearance order (user_hashmap's; missing: "")
+    dst_keys: list
+    counts: np.ndarray         # int64 (len(src_keys), len(dst_keys)): pod pairs g -> h
+    src_sizes: np.ndarray      # pods per source group among the held rows
+    dst_sizes: np.ndarray      # pods per destination group
+
+    def pairs(self, cross_only: bool = True) -> List[Tuple]:
+        """[(src_key, dst_key, count)] for every count > 0, in row-major
+        order; ``cross_only`` drops the entries with src_key == dst_key."""
+        out = []
+        for g, h in np.argwhere(np.asarray(self.counts) > 0).tolist():
+            s, d = self.src_keys[g], self.dst_keys[h]
+            if cross_only and s == d:
+                continue
+            out.append((s, d, int(self.counts[g][h])))
+        return out
+
+
+def _group_engine(matrix: ReachabilityMatrix, containers: List[Container]):
+    eng = _engine(matrix, whole=False)
+    n = matrix.container_size
+    if len(containers) != n:
+        raise ValueError("bitarrays of equal length expected for bitwise operation")
+    return eng, n, (getattr(eng, "row_span", None) or (0, n))
+
+
+def group_reachability(matrix: ReachabilityMatrix, containers: List[Container], label: str,
+                       dst_label: Optional[str] = None) -> GroupReachability:
+    """The pod pairs (i, j) with M[i, j] = 1 counted by the group of i under
+    ``label`` and the group of j under ``dst_label`` (default: ``label``).
+    A matrix holding a row shard counts its own rows' pairs."""
+    eng, n, (r0, r1) = _group_engine(matrix, containers)
+    skeys, gs = group_keys(containers, label)
+    dkeys, gd = (skeys, gs) if dst_label is None else group_keys(containers, dst_label)
+    Gs, Gd = len(skeys), len(dkeys)
+    if n == 0:
+        return GroupReachability([], [], np.zeros((0, 0), np.int64), np.zeros(0, np.int64),
+                                 np.zeros(0, np.int64))
+    counts = eng.group_counts(gs, gd, Gs, Gd)["counts"]
+    return GroupReachability(skeys, dkeys, counts,
+                             np.bincount(gs[r0:r1], minlength=Gs).astype(np.int64),
+                             np.bincount(gd, minlength=Gd).astype(np.int64))
+
+
+def group_fanout(matrix: ReachabilityMatrix, containers: List[Container], label: str,
+                 rows: Optional[Tuple[int, int]] = None) -> Tuple[list, np.ndarray]:
+    """Per held source pod, the number of pods it reaches in every group of
+    ``label``: (dst_keys, int32 array (rows, G)), one row per held row in row
+    order (a row shard: its rows); ``rows`` = (r0, r1) keeps those sources."""
+    eng, n, span = _group_engine(matrix, containers)
+    keys, gd = group_keys(containers, label)
+    r0, r1 = span if rows is None else (int(rows[0]), int(rows[1]))
+    if not span[0] <= r0 <= r1 <= span[1]:
+        raise ValueError(f"rows [{r0}, {r1}) outside the held rows [{span[0]}, {span[1]})")
+    if n == 0:
+        return [], np.zeros((0, 0), np.int32)
+    out = eng.group_counts(np.full(n, -1, np.int32), gd, 1, len(keys), rows=True)["row_counts"]
+    return keys, out[r0 - span[0]:r1 - span[0]]
+
+
+def reach_count(matrix: ReachabilityMatrix, sources, dests) -> int:
+    """The pairs (i, j) with M[i, j] = 1, i in the index set ``sources`` and
+    j in the index set ``dests``.  A matrix holding a row shard counts the
+    sources among its rows."""
+    eng = _engine(matrix, whole=False)
+    n = matrix.container_size
+    if n == 0:
+        return 0
+    gs, gd = np.full(n, -1, np.int32), np.full(n, -1, np.int32)
+    gs[np.asarray(list(sources), dtype=np.int64)] = 0
+    gd[np.asarray(list(dests), dtype=np.int64)] = 0
+    return int(eng.group_counts(gs, gd, 1, 1)["counts"][0, 0])
 
 
 # ---------------------------------------------------------------------------

@@ -496,6 +496,22 @@ class MultiBuild:
         for m, s in zip(self.members, src.members):
             m.copy_from(s)
 
+    # -- group_reachability -------------------------------------------------------
+    def group_counts(self, gs, gd, Gs: Optional[int] = None, Gd: Optional[int] = None,
+                     rows: bool = False) -> dict:
+        """DeviceBuild.group_counts over the row-sharded matrix: the members'
+        counts summed, their row counts concatenated in rank (= row) order."""
+        gs = np.ascontiguousarray(gs, dtype=np.int32).reshape(-1)
+        gd = np.ascontiguousarray(gd, dtype=np.int32).reshape(-1)
+        if Gs is None:
+            Gs = max(int(gs.max()) + 1, 1) if gs.size else 1
+        if Gd is None:
+            Gd = max(int(gd.max()) + 1, 1) if gd.size else 1
+        parts = [m.group_counts(gs, gd, Gs, Gd, rows=rows) for m in self.members]
+        counts = np.sum([p["counts"] for p in parts], axis=0, dtype=np.int64)
+        return dict(counts=counts,
+                    row_counts=np.concatenate([p["row_counts"] for p in parts]) if rows else None)
+
     # -- measurement ------------------------------------------------------------
     def exchange_timing(self, enable: Optional[bool] = None, reset: bool = False) -> dict:
         """The verify exchange's time on member 0's stream (HIP events around
