@@ -217,6 +217,49 @@ int kano_policy_impact_lists(kano_ctx* ctx, int64_t n_lists, int64_t nbits, int6
                              const uint64_t* allow_rows, int mode,
                              int64_t* impact, uint8_t* essential, int64_t* n_redundant);
 
+/* pair_policies: which policies allow a given pod pair.  Over the working
+ * sets of the matrix's current policies (the build's that are not removed,
+ * plus the added ones that are not removed),
+ *   pols(i,j)  = the ascending engine ids p with i in select_p, j in allow_p,
+ *   cover(i,j) = the length of pols(i,j)
+ * for Q query pairs (i,j) = pairs[2q], pairs[2q+1], in any order, duplicates
+ * allowed.  A policy appears at most once per pair.  The query speaks about
+ * the policies, not about bits edited with kano_set_bit / kano_put_rows: on
+ * an unedited matrix cover(i,j) > 0 iff M[i,j] = 1.  Unlike
+ * kano_policy_impact it accepts a context after kano_add_policies /
+ * kano_remove_policies (the added policies carry the ids P, P+1, ... that
+ * kano_add_policies returned; removed ids never appear).
+ * mode 0: cover[Q] (nullable), off[Q+1] (nullable; pair q's ids are
+ * pol[off[q] .. off[q+1]) of kano_pair_policies_fetch), hist[P + added]
+ * (nullable; hist[p] = the queried pairs p allows) and *total = off[Q] =
+ * sum of cover (nullable).  mode 1: cover, hist and *total only, no lists on
+ * the device and off untouched; kano_pair_policies_fetch then returns
+ * -EINVAL, as it does before any call.  Any other mode returns -EINVAL; Q < 0
+ * or NULL pairs with Q > 0 -EINVAL; an index outside [0, n) -ERANGE; Q = 0 is
+ * valid.  A context whose matrix has no policies (an empty, copied, loaded,
+ * path or edge matrix) returns -EINVAL.  On a row shard a pair whose i lies
+ * outside r0..r1 gets cover 0 and no ids and adds nothing to hist, so the
+ * covers and histograms of row shards add up and every list comes from the
+ * shard holding i.  Exact integers.  The device buffers are the call's own:
+ * the shadow, conflict and impact fetches after it return their own results,
+ * a call between pipelined kano_verify steps leaves the next step unchanged,
+ * and a failed allocation returns -ENOMEM and leaves the context usable. */
+int kano_pair_policies(kano_ctx* ctx, int64_t Q, const int32_t* pairs /* 2*Q */, int mode,
+                       int32_t* cover /* Q, nullable */, int64_t* off /* Q+1, nullable */,
+                       int64_t* hist /* P_total, nullable */, int64_t* total);
+int kano_pair_policies_fetch(kano_ctx* ctx, int32_t* pol /* total */);
+/* The same over explicit inputs (the arguments of kano_shadow_lists): a pair
+ * is (list index, bit index).  An id repeated within one list counts once; an
+ * id outside [0, P) returns -ERANGE.  The context holds no matrix afterwards. */
+int kano_pair_policies_lists(kano_ctx* ctx, int64_t n_lists, int64_t nbits, int64_t P,
+                             const int64_t* soff, const int32_t* slist,
+                             const uint64_t* allow_rows, int64_t Q, const int32_t* pairs,
+                             int mode, int32_t* cover, int64_t* off, int64_t* hist,
+                             int64_t* total);
+/* KANO_TUNE timing=1: the last call's device time (the fill, the count pass,
+ * the offsets' scan and the emit pass; no copies). */
+int kano_pair_policies_time(kano_ctx* ctx, float* ms);
+
 /* matrix_diff: what a change adds and removes.  a and b hold matrices of the
  * same n on the same device over the same rows r0..r1 (built, loaded, path or
  * edge matrices alike); for i in [r0, r1), j in [0, n):

@@ -164,6 +164,8 @@ struct kano_ctx {
   int rows_cww = MAX_CWW_KNOB;   // cww: k_rows column chunk (words); the chunking wide matrices
                              // (n > 524k) take, forced at small n
   int impact_form = 0;       // impf=1/2: policy_impact's list / row form forced (0: by density)
+  int pair_form = 0;         // ppf=1/2: pair_policies' lane / wave form forced (0: by list length)
+  int pair_grid = 0;         // ppgrid=K: at most K blocks for k_pair_lane / k_pair_wave (0: 8 per CU)
   int diff_grid = 0;         // dgrid=K: at most K blocks for k_diff_rows (0: every resident block)
   int group_grid = 0;        // ggrid=K: at most K blocks for k_group_rows (0: every resident block)
   int group_batches = 0;     // gbatch=K: at most K batches of 64 destination groups in one
@@ -258,6 +260,12 @@ struct kano_ctx {
   // sums and essential flags, no other buffer written
   DBuf impact_out, impact_ess;
   float impact_ms = 0.f;      // timing=1: the last call's device time (fill + kernel)
+  // pair_policies (kano_pair_policies): the query's own buffers -- the pairs,
+  // the counts, the offsets, the histogram, the alive flags and the id lists
+  // kano_pair_policies_fetch copies out (pair_total < 0: none to fetch)
+  DBuf pp_pairs, pp_cover, pp_off, pp_hist, pp_dead, pp_pol;
+  i64 pair_total = -1;
+  float pair_ms = 0.f;        // timing=1: the last call's fills + kernels + scan (no copies)
   // matrix_diff (kano_diff / kano_diff_pairs, in the second context b): the
   // totals, column words and row counts of the last call, no other buffer
   // written (the offsets and pairs of kano_diff_pairs are temporaries)

@@ -2303,6 +2303,8 @@ int kano_create(int device, kano_ctx** out) {
         if (k == "pathtn" && (v == 2 || v == 4)) ctx->path_tn = v;
         if (k == "shgsub") ctx->shg_sub_lds = v;
         if (k == "impf" && v >= 0 && v <= 2) ctx->impact_form = v;
+        if (k == "ppf" && v >= 0 && v <= 2) ctx->pair_form = v;
+        if (k == "ppgrid" && v >= 0) ctx->pair_grid = v;
         if (k == "dgrid" && v >= 0) ctx->diff_grid = v;
         if (k == "ggrid" && v >= 0) ctx->group_grid = v;
         if (k == "gbatch" && v >= 0) ctx->group_batches = v;
@@ -2482,6 +2484,8 @@ void kano_destroy(kano_ctx* ctx) {
                   &ctx->flags,  &ctx->T,       &ctx->loff,    &ctx->L,         &ctx->tp,
                   &ctx->poff,   &ctx->out,     &ctx->conflict_out, &ctx->scratch_words, &ctx->ident, &ctx->ecls,
                   &ctx->impact_out, &ctx->impact_ess, &ctx->diff_buf,
+                  &ctx->pp_pairs, &ctx->pp_cover, &ctx->pp_off, &ctx->pp_hist, &ctx->pp_dead,
+                  &ctx->pp_pol,
                   &ctx->tcnt,   &ctx->toff,    &ctx->sizes,   &ctx->icnt,      &ctx->ioff,
                   &ctx->sysrow, &ctx->wicls,   &ctx->idxd,
                   &ctx->ckey,   &ctx->corder,  &ctx->kcnt,    &ctx->koff,
@@ -3829,6 +3833,202 @@ int kano_policy_impact_lists(kano_ctx* ctx, int64_t n_lists, int64_t nbits, int6
   }
   KTRY(lists_setup(ctx, "kano_policy_impact_lists", n_lists, nbits, P, soff, slist, allow_rows));
   return impact_run(ctx, mode, impact, essential, n_redundant);
+}
+
+}  // extern "C"
+
+namespace {
+// pair_policies on the resident tables (k_pair_lane / k_pair_wave): the count
+// pass, in mode 0 the offsets' scan and the emit pass.  Only the pp_* buffers
+// are written (and the scans' scratch): policy_shadow's, policy_conflict's and
+// policy_impact's results and kano_verify's state stay as they are.  The
+// tables are the build's; the added policies are read from their pod-level
+// sets and the removed ones skipped by their flags, so an updated matrix is
+// answered as it stands.
+int pair_run(kano_ctx* ctx, const char* what, i64 Q, const int32_t* pairs, int mode,
+             int32_t* cover, int64_t* off, int64_t* hist, int64_t* total) {
+  const std::string w(what);
+  ctx->pair_total = -1;
+  if (total) *total = 0;
+  if (Q < 0 || (Q > 0 && !pairs)) return fail(ctx, -EINVAL, w + ": bad arguments");
+  const bool lists = ctx->lists_mode;
+  const i64 P = ctx->P, A = lists ? 0 : ctx->inc_A, PT = P + A;
+  const i64 ni = lists ? ctx->rc.U : ctx->n, nj = ctx->n;
+  for (i64 q = 0; q < Q; ++q)
+    if (pairs[2 * q] < 0 || pairs[2 * q] >= ni || pairs[2 * q + 1] < 0 || pairs[2 * q + 1] >= nj)
+      return fail(ctx, -ERANGE, w + ": pair " + std::to_string(q) + " out of range");
+  if (hist && PT > 0) std::memset(hist, 0, sizeof(int64_t) * (size_t)PT);
+  if (Q == 0) {
+    if (mode == 0) {
+      if (off) off[0] = 0;
+      ctx->pair_total = 0;
+    }
+    return 0;
+  }
+  const bool any_dead =
+      !lists && std::find(ctx->dead.begin(), ctx->dead.end(), 1) != ctx->dead.end();
+  KTRY(dalloc(ctx, ctx->pp_pairs, sizeof(int32_t) * 2 * (size_t)Q));
+  KTRY(dalloc(ctx, ctx->pp_cover, sizeof(int32_t) * (size_t)Q));
+  if (mode == 0) KTRY(dalloc(ctx, ctx->pp_off, sizeof(i64) * (size_t)(Q + 1)));
+  if (hist) KTRY(dalloc(ctx, ctx->pp_hist, sizeof(i64) * (size_t)std::max<i64>(1, PT)));
+  if (any_dead) KTRY(dalloc(ctx, ctx->pp_dead, (size_t)PT));
+  KCHK(hipMemcpyAsync(ctx->pp_pairs.p, pairs, sizeof(int32_t) * 2 * (size_t)Q,
+                      hipMemcpyHostToDevice, ctx->stream));
+  if (any_dead)
+    KCHK(hipMemcpyAsync(ctx->pp_dead.p, ctx->dead.data(), (size_t)PT, hipMemcpyHostToDevice,
+                        ctx->stream));
+  PairArgs a{};
+  a.pairs = P_<int32_t>(ctx->pp_pairs);
+  a.Q = Q;
+  // (a build without policies has no classes: only the added part remains)
+  a.rcls = P > 0 && ctx->rc.U > 0 ? P_<int32_t>(ctx->rc.cls) : nullptr;
+  a.ccls = lists ? nullptr : P_<int32_t>(ctx->cc.cls);   // lists: every pod a class
+  a.soffc = P_<i64>(ctx->soffc);
+  a.slist = P_<int32_t>(ctx->slist);
+  a.dead = any_dead ? P_<uint8_t>(ctx->pp_dead) : nullptr;
+  a.AC = P_<u64>(ctx->AC);
+  a.ldC = ctx->ldC;
+  a.P = P;
+  a.asel = P_<u64>(ctx->asel);
+  a.aalw = P_<u64>(ctx->aalw);
+  a.W = ctx->W;
+  a.A = A;
+  a.r0 = ctx->r0;
+  a.r1 = ctx->r1;
+  a.cover = P_<int32_t>(ctx->pp_cover);
+  a.hist = hist ? P_<i64>(ctx->pp_hist) : nullptr;
+  if (a.rcls && !lists && !a.ccls) return fail(ctx, -EINVAL, w + ": no column classes");
+  // The form, from the mean list a pair walks (s = policies per row class,
+  // plus the added ones): a lane per pair makes that many dependent loads, a
+  // wave per pair ceil(s / 64) rounds on 1/64 of the pairs in flight.
+  const i64 U = ctx->rc.U;
+  const i64 sbar = (a.rcls ? (ctx->nnz_sel + U - 1) / U : 0) + A;
+  bool wave = sbar > PAIR_WAVE_MIN;
+  if (ctx->pair_form) wave = ctx->pair_form == 2;
+  const i64 cap = ctx->pair_grid > 0 ? ctx->pair_grid : (i64)std::max(1, ctx->num_cus) * 8;
+  const unsigned grid = (unsigned)std::min<i64>(cap, wave ? (Q + WPB - 1) / WPB : nblk(Q));
+  // timing=1: the call's device time, [0, 1] the fill, the count pass and the
+  // scan, [2, 3] the emit pass (the host reads the total in between)
+  hipEvent_t tev[4] = {nullptr, nullptr, nullptr, nullptr};
+  if (ctx->stage_timing) {
+    for (auto& e : tev) KCHK(hipEventCreate(&e));
+    KCHK(hipEventRecord(tev[0], ctx->stream));
+  }
+  if (hist && PT > 0) KCHK(hipMemsetAsync(ctx->pp_hist.p, 0, sizeof(i64) * (size_t)PT, ctx->stream));
+  // (direct launches, no kernel-pointer variable: tests/test_launch_ir.py)
+  if (wave) hipLaunchKernelGGL((k_pair_wave<false>), dim3(grid), dim3(TPB), 0, ctx->stream, a);
+  else hipLaunchKernelGGL((k_pair_lane<false>), dim3(grid), dim3(TPB), 0, ctx->stream, a);
+  KLAUNCH();
+  if (mode == 0)
+    KTRY((scan_excl<int32_t, i64>(ctx, P_<int32_t>(ctx->pp_cover), Q, P_<i64>(ctx->pp_off))));
+  if (tev[0]) KCHK(hipEventRecord(tev[1], ctx->stream));
+  i64 tot = 0;
+  std::vector<int32_t> own;
+  if (mode == 0) {
+    KCHK(hipMemcpyAsync(&tot, P_<i64>(ctx->pp_off) + Q, sizeof(i64), hipMemcpyDeviceToHost,
+                        ctx->stream));
+    KTRY(sync(ctx));
+    KTRY(dalloc(ctx, ctx->pp_pol, sizeof(int32_t) * (size_t)std::max<i64>(1, tot)));
+    if (tev[0]) KCHK(hipEventRecord(tev[2], ctx->stream));
+    if (tot > 0) {
+      a.off = P_<i64>(ctx->pp_off);
+      a.pol = P_<int32_t>(ctx->pp_pol);
+      a.cap = tot;
+      if (wave) hipLaunchKernelGGL((k_pair_wave<true>), dim3(grid), dim3(TPB), 0, ctx->stream, a);
+      else hipLaunchKernelGGL((k_pair_lane<true>), dim3(grid), dim3(TPB), 0, ctx->stream, a);
+      KLAUNCH();
+    }
+    if (tev[0]) KCHK(hipEventRecord(tev[3], ctx->stream));
+    if (off)
+      KCHK(hipMemcpyAsync(off, ctx->pp_off.p, sizeof(i64) * (size_t)(Q + 1), hipMemcpyDeviceToHost,
+                          ctx->stream));
+  } else if (!cover && total) {
+    own.resize((size_t)Q);
+    cover = own.data();
+  }
+  if (cover)
+    KCHK(hipMemcpyAsync(cover, ctx->pp_cover.p, sizeof(int32_t) * (size_t)Q, hipMemcpyDeviceToHost,
+                        ctx->stream));
+  if (hist && PT > 0)
+    KCHK(hipMemcpyAsync(hist, ctx->pp_hist.p, sizeof(i64) * (size_t)PT, hipMemcpyDeviceToHost,
+                        ctx->stream));
+  KTRY(sync(ctx));
+  if (tev[0]) {
+    float ms = 0.f, ms2 = 0.f;
+    (void)hipEventElapsedTime(&ms, tev[0], tev[1]);
+    if (mode == 0) (void)hipEventElapsedTime(&ms2, tev[2], tev[3]);
+    ctx->pair_ms = ms + ms2;
+    for (auto& e : tev) (void)hipEventDestroy(e);
+  }
+  if (mode == 0) {
+    ctx->pair_total = tot;
+  } else if (total) {
+    for (i64 q = 0; q < Q; ++q) tot += cover[q];
+  }
+  if (total) *total = tot;
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int kano_pair_policies(kano_ctx* ctx, int64_t Q, const int32_t* pairs, int mode, int32_t* cover,
+                       int64_t* off, int64_t* hist, int64_t* total) {
+  KTRY(ensure_built(ctx));
+  ctx->pair_total = -1;
+  if (mode != 0 && mode != 1) return fail(ctx, -EINVAL, "kano_pair_policies: unknown mode");
+  if (!ctx->lists_mode && ctx->P == 0 && ctx->inc_A == 0)
+    return fail(ctx, -EINVAL,
+                "kano_pair_policies: the matrix has no policies (an empty, copied, loaded, "
+                "path or edge matrix holds rows only)");
+  return pair_run(ctx, "kano_pair_policies", Q, pairs, mode, cover, off, hist, total);
+}
+
+int kano_pair_policies_fetch(kano_ctx* ctx, int32_t* pol) {
+  KTRY(ensure_built(ctx));
+  if (ctx->pair_total < 0)
+    return fail(ctx, -EINVAL, "kano_pair_policies_fetch before kano_pair_policies (mode 0)");
+  if (ctx->pair_total > 0) {
+    if (!pol) return fail(ctx, -EINVAL, "kano_pair_policies_fetch: NULL buffer");
+    KCHK(hipMemcpyAsync(pol, ctx->pp_pol.p, sizeof(int32_t) * (size_t)ctx->pair_total,
+                        hipMemcpyDeviceToHost, ctx->stream));
+  }
+  return sync(ctx);
+}
+
+int kano_pair_policies_lists(kano_ctx* ctx, int64_t n_lists, int64_t nbits, int64_t P,
+                             const int64_t* soff, const int32_t* slist,
+                             const uint64_t* allow_rows, int64_t Q, const int32_t* pairs, int mode,
+                             int32_t* cover, int64_t* off, int64_t* hist, int64_t* total) {
+  if (!ctx) return -EINVAL;
+  ctx->pair_total = -1;
+  if (mode != 0 && mode != 1)
+    return fail(ctx, -EINVAL, "kano_pair_policies_lists: unknown mode");
+  if (n_lists < 0 || nbits < 0 || P < 0 || !soff || soff[0] < 0 ||
+      (soff[n_lists] > soff[0] && !slist))
+    return fail(ctx, -EINVAL, "kano_pair_policies_lists: bad arguments");
+  // every list ascending with its ids once (pols(i, j) is a set, ascending)
+  std::vector<int64_t> so((size_t)n_lists + 1, 0);
+  std::vector<int32_t> sl;
+  sl.reserve((size_t)std::max<int64_t>(0, soff[n_lists]));
+  for (i64 c = 0; c < n_lists; ++c) {
+    if (soff[c + 1] < soff[c])
+      return fail(ctx, -EINVAL, "kano_pair_policies_lists: offsets not ascending");
+    const size_t b = sl.size();
+    sl.insert(sl.end(), slist + soff[c], slist + soff[c + 1]);
+    std::sort(sl.begin() + b, sl.end());
+    sl.erase(std::unique(sl.begin() + b, sl.end()), sl.end());
+    so[c + 1] = (int64_t)sl.size();
+  }
+  KTRY(lists_setup(ctx, "kano_pair_policies_lists", n_lists, nbits, P, so.data(), sl.data(),
+                   allow_rows));
+  return pair_run(ctx, "kano_pair_policies_lists", Q, pairs, mode, cover, off, hist, total);
+}
+
+int kano_pair_policies_time(kano_ctx* ctx, float* ms) {
+  if (!ctx || !ms) return -EINVAL;
+  *ms = ctx->pair_ms;
+  return 0;
 }
 
 }  // extern "C"

@@ -3205,6 +3205,227 @@ __global__ __launch_bounds__(TPB) void k_impact_rows(ImpactArgs a) {
   }
 }
 
+// ===========================================================================
+// pair_policies: which policies allow a given pod pair.
+//   pols(i, j)  = ascending engine ids p with i in sel_p and j in allow_p
+//   cover(i, j) = |pols(i, j)|
+// over the matrix's current policies.  For a query pair (i, j) with row class
+// c = rcls[i] and column class x = ccls[j] (lists mode: ccls null, x = j) the
+// build's part is every alive p of S(c) whose bit x is set in AC[p]; the
+// added policies (ids P + q) are tested on their pod-level sets asel / aalw.
+// S(c) is ascending and the added ids follow the build's, so every pair's ids
+// come out ascending from a serial walk or a ballot prefix.  A pair whose i
+// lies outside [r0, r1) (another shard's row) has no policies here.
+//
+// One walk, two passes: EMIT = false counts (cover[q], and hist[p] += 1 per
+// listed policy when hist is given), EMIT = true writes the ids at off[q]
+// (the exclusive scan of the counts).  Two forms, chosen per call by the host:
+//   k_pair_lane  a lane per pair, S(c) walked serially (short lists); the
+//                histogram merges the lanes of a wave that hit one policy
+//   k_pair_wave  a wave per pair, the lanes striding S(c), ballot + popcount
+//                for the count and the emit position (long lists); the ids of
+//                one pair are distinct, so its lanes never share a policy; a
+//                wave takes a contiguous run of pairs and sums a lane's hits
+//                of one policy in registers (PairAcc)
+// k_pair_lane is grid-stride over the pairs.
+// ===========================================================================
+struct PairArgs {
+  const int32_t* pairs;  // (i, j) x Q
+  i64 Q;
+  const int32_t* rcls;   // null: the build had no policies (only the added part)
+  const int32_t* ccls;   // null: x = j
+  const i64* soffc;
+  const int32_t* slist;
+  const uint8_t* dead;   // P + A flags; null: none removed
+  const u64* AC;
+  i64 ldC;
+  i64 P;
+  const u64* asel;
+  const u64* aalw;
+  i64 W, A;
+  i64 r0, r1;
+  int32_t* cover;        // !EMIT
+  i64* hist;             // !EMIT, nullable
+  const i64* off;        // EMIT
+  int32_t* pol;          // EMIT
+  i64 cap;               // EMIT: entries of pol
+};
+
+// the wave form when a pair walks more than this many policies on average
+// (mean |S(c)| + added policies; the host's choice, kano_hip.hip pair_run)
+constexpr i64 PAIR_WAVE_MIN = 16;
+
+// hist[key] += 1 for every active lane, lanes with equal keys merged into one
+// 64-bit atomic (as wave_agg_inc).  Every lane of the wave must call it.
+__device__ __forceinline__ void wave_agg_add64(i64* hist, i64 key, bool active) {
+  const int lane = threadIdx.x & 63;
+  u64 rem = __ballot(active);
+  bool done = !active;
+  for (int round = 0; round < AGG_ROUNDS && rem; ++round) {
+    const int leader = __ffsll((long long)rem) - 1;
+    const i64 k0 = __shfl(key, leader, 64);
+    const bool same = !done && key == k0;
+    const u64 smask = __ballot(same);
+    if (lane == leader)
+      atomicAdd(reinterpret_cast<unsigned long long*>(&hist[k0]),
+                (unsigned long long)__popcll(smask));
+    if (same) done = true;
+    rem &= ~smask;
+  }
+  if (!done) atomicAdd(reinterpret_cast<unsigned long long*>(&hist[key]), 1ull);
+}
+
+template <bool EMIT>
+__global__ __launch_bounds__(TPB) void k_pair_lane(PairArgs a) {
+  const i64 stride = (i64)gridDim.x * TPB;
+  // (whole waves leave together: the loop bound is the wave's first pair)
+  for (i64 q0 = (i64)blockIdx.x * TPB + (threadIdx.x & ~63); q0 < a.Q; q0 += stride) {
+    const i64 q = q0 + (threadIdx.x & 63);
+    i64 i = 0, j = 0, s0 = 0, s = 0, x = 0;
+    bool own = false;
+    if (q < a.Q) {
+      i = a.pairs[2 * q];
+      j = a.pairs[2 * q + 1];
+      own = i >= a.r0 && i < a.r1;
+      if (own && a.rcls) {
+        const int32_t c = a.rcls[i];
+        s0 = a.soffc[c];
+        s = a.soffc[c + 1] - s0;
+        x = a.ccls ? a.ccls[j] : j;
+      }
+    }
+    i64 o = EMIT && q < a.Q ? a.off[q] : 0;
+    int32_t cnt = 0;
+    for (i64 k = 0; __ballot(k < s) != 0ull; ++k) {
+      int32_t p = 0;
+      bool hit = false;
+      if (k < s) {
+        p = a.slist[s0 + k];
+        hit = !(a.dead && a.dead[p]) && ((a.AC[(i64)p * a.ldC + (x >> 6)] >> (x & 63)) & 1ull);
+      }
+      if (EMIT) {
+        if (hit && o < a.cap) a.pol[o] = p;
+        o += hit;
+      } else {
+        cnt += hit;
+        if (a.hist) wave_agg_add64(a.hist, p, hit);
+      }
+    }
+    for (i64 t = 0; t < a.A; ++t) {
+      const bool hit = own && !(a.dead && a.dead[a.P + t]) &&
+                       ((a.asel[t * a.W + (i >> 6)] >> (i & 63)) & 1ull) &&
+                       ((a.aalw[t * a.W + (j >> 6)] >> (j & 63)) & 1ull);
+      if (EMIT) {
+        if (hit && o < a.cap) a.pol[o] = (int32_t)(a.P + t);
+        o += hit;
+      } else {
+        cnt += hit;
+        if (a.hist) wave_agg_add64(a.hist, a.P + t, hit);
+      }
+    }
+    if (!EMIT && q < a.Q) a.cover[q] = cnt;
+  }
+}
+
+// A lane's pending histogram add in the wave form: n hits of policy p not yet
+// in hist.  The wave takes a contiguous run of pairs, and pairs sorted by i
+// (a diff's output) share the row class from one pair to the next, so lane k
+// of round r meets the same policy again and again: the hits are summed in
+// registers and added when the policy changes (and at the end).  A set of
+// violating pairs blamed on a few policies would otherwise serialise every
+// wave's atomics on their few counters.
+struct PairAcc {
+  int32_t p, n;
+};
+__device__ __forceinline__ void pair_acc_flush(i64* hist, PairAcc& c) {
+  if (c.n) atomicAdd(reinterpret_cast<unsigned long long*>(&hist[c.p]), (unsigned long long)c.n);
+  c.n = 0;
+}
+__device__ __forceinline__ void pair_acc_add(i64* hist, PairAcc& c, int32_t p) {
+  if (c.p != p) {
+    pair_acc_flush(hist, c);
+    c.p = p;
+  }
+  ++c.n;
+}
+constexpr int PAIR_ACC = 4;   // rounds of S(c) (64 policies each) summed that way; the
+                              // later rounds of a longer list add one by one
+
+template <bool EMIT>
+__global__ __launch_bounds__(TPB) void k_pair_wave(PairArgs a) {
+  const int lane = threadIdx.x & 63;
+  const u64 below = (1ull << lane) - 1ull;
+  // wave gw of nw takes pairs [gw * per, (gw + 1) * per)
+  const i64 nw = (i64)gridDim.x * WPB, gw = (i64)blockIdx.x * WPB + (threadIdx.x >> 6);
+  const i64 per = (a.Q + nw - 1) / nw;
+  const i64 q1 = min(a.Q, (gw + 1) * per);
+  PairAcc acc[PAIR_ACC + 1];   // (the last one: the first 64 added policies)
+#pragma unroll
+  for (int r = 0; r <= PAIR_ACC; ++r) acc[r] = PairAcc{0, 0};
+  for (i64 q = gw * per; q < q1; ++q) {          // wave-uniform
+    const i64 i = a.pairs[2 * q], j = a.pairs[2 * q + 1];
+    const bool own = i >= a.r0 && i < a.r1;
+    i64 o = EMIT ? a.off[q] : 0;
+    int32_t cnt = 0;
+    // one round: lanes k = b + lane of the list; ac: where the histogram sums
+    auto round = [&](i64 s0, i64 s, i64 x, i64 b, PairAcc* ac) {
+      const i64 k = b + lane;
+      int32_t p = 0;
+      bool hit = false;
+      if (k < s) {
+        p = a.slist[s0 + k];
+        hit = !(a.dead && a.dead[p]) && ((a.AC[(i64)p * a.ldC + (x >> 6)] >> (x & 63)) & 1ull);
+      }
+      const u64 bal = __ballot(hit);
+      if (EMIT) {
+        const i64 at = o + __popcll(bal & below);
+        if (hit && at < a.cap) a.pol[at] = p;
+        o += __popcll(bal);
+      } else {
+        cnt += __popcll(bal);
+        if (hit && a.hist) {
+          if (ac) pair_acc_add(a.hist, *ac, p);
+          else atomicAdd(reinterpret_cast<unsigned long long*>(&a.hist[p]), 1ull);
+        }
+      }
+    };
+    if (own && a.rcls) {
+      const int32_t c = a.rcls[i];
+      const i64 s0 = a.soffc[c], s = a.soffc[c + 1] - s0;
+      const i64 x = a.ccls ? a.ccls[j] : j;
+#pragma unroll
+      for (int r = 0; r < PAIR_ACC; ++r)
+        if ((i64)r * 64 < s) round(s0, s, x, (i64)r * 64, &acc[r]);
+      for (i64 b = (i64)PAIR_ACC * 64; b < s; b += 64) round(s0, s, x, b, nullptr);
+    }
+    if (own) {
+      for (i64 b = 0; b < a.A; b += 64) {
+        const i64 t = b + lane;
+        const bool hit = t < a.A && !(a.dead && a.dead[a.P + t]) &&
+                         ((a.asel[t * a.W + (i >> 6)] >> (i & 63)) & 1ull) &&
+                         ((a.aalw[t * a.W + (j >> 6)] >> (j & 63)) & 1ull);
+        const u64 bal = __ballot(hit);
+        if (EMIT) {
+          const i64 at = o + __popcll(bal & below);
+          if (hit && at < a.cap) a.pol[at] = (int32_t)(a.P + t);
+          o += __popcll(bal);
+        } else {
+          cnt += __popcll(bal);
+          if (hit && a.hist) {
+            if (b == 0) pair_acc_add(a.hist, acc[PAIR_ACC], (int32_t)(a.P + t));
+            else atomicAdd(reinterpret_cast<unsigned long long*>(&a.hist[a.P + t]), 1ull);
+          }
+        }
+      }
+    }
+    if (!EMIT && lane == 0) a.cover[q] = cnt;
+  }
+  if (!EMIT && a.hist) {
+#pragma unroll
+    for (int r = 0; r <= PAIR_ACC; ++r) pair_acc_flush(a.hist, acc[r]);
+  }
+}
+
 // ---------------------------------------------------------------------------
 // policy_shadow's pair count without the pairs (kano_verify, shadow_cap < 0):
 // algorithm.py:58-80 counts, per pod i, the ordered pairs j != k of S(i) with

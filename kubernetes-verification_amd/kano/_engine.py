@@ -242,6 +242,8 @@ class DeviceBuild:
         self._chk(self.lib.kano_add_policies(
             self.ctx, int(so.shape[0] - 1), int(xv.shape[0]), _ptr(xv), _ptr(so), _ptr(sc),
             _ptr(sv), _ptr(ao), _ptr(ac), _ptr(av), byref(first)), "kano_add_policies")
+        # (engine ids in use: the build's and every added one, removed or not)
+        self._id_end = int(first.value) + int(so.shape[0] - 1)
         return int(first.value)
 
     def remove_policies(self, ids) -> None:
@@ -619,6 +621,33 @@ class DeviceBuild:
                   "kano_policy_impact")
         return out.astype(bool)
 
+    # -- pair_policies (kano_pair_policies) -------------------------------
+    def pair_policies(self, pairs, lists: bool = True, hist: bool = False,
+                      nids: Optional[int] = None) -> dict:
+        """Which of the matrix's current policies allow each pod pair of
+        ``pairs`` ((Q, 2) int32: i selected, j allowed): ``cover`` (int32, Q),
+        with ``lists`` also ``offsets`` (int64, Q + 1) and ``policies`` (int32:
+        pair q's ascending engine ids are policies[offsets[q]:offsets[q + 1]];
+        else both None), with ``hist`` the queried pairs every engine id
+        allows (int64; else None).  Works after add_policies /
+        remove_policies; a row shard answers for the pairs whose i it holds
+        (the others get cover 0).  ``nids``: the engine ids in use (default:
+        the build's policies and the ones added through this object)."""
+        pr, Q = _as_pairs(pairs)
+        if nids is None:            # (the added ids follow the build's P)
+            nids = max(self.info()["P"], getattr(self, "_id_end", 0))
+        return _pair_call(
+            lambda *out: self.lib.kano_pair_policies(self.ctx, Q, _ptr(pr), 0 if lists else 1,
+                                                     *out),
+            self, "kano_pair_policies", Q, lists, int(nids) if hist else None)
+
+    def pair_policies_time(self) -> float:
+        """The last pair_policies' device time (ms; KANO_TUNE=timing=1)."""
+        ms = ctypes.c_float(0.0)
+        self._chk(self.lib.kano_pair_policies_time(self.ctx, byref(ms)),
+                  "kano_pair_policies_time")
+        return float(ms.value)
+
     # -- matrix_diff (kano_diff / kano_diff_pairs / kano_copy_matrix) -----
     DIFF_KINDS = {"added": 0, "removed": 1}
 
@@ -770,6 +799,64 @@ class DeviceBuild:
         return dict(classes=float(ms[0]), allow=float(ms[1]), select=float(ms[2]),
                     rows=float(ms[3]), shadow=float(ms[4]), build=float(ms[5]),
                     k_rows=float(ms[6]), impact=float(ms[7]))
+
+
+def _as_pairs(pairs) -> Tuple[np.ndarray, int]:
+    """Query pairs as a C-contiguous (Q, 2) int32 array (what diff_pairs
+    returns, or a list of (i, j) tuples) and Q."""
+    a = np.asarray(pairs)
+    if a.size == 0:
+        return np.zeros((0, 2), dtype=np.int32), 0
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError("pairs must be a (Q, 2) array or a list of (i, j) tuples")
+    if a.dtype != np.int32:
+        if not np.issubdtype(a.dtype, np.integer):
+            raise TypeError("pairs must hold integers")
+        if a.min() < -2 ** 31 or a.max() >= 2 ** 31:
+            raise IndexError("pair index out of range")
+    return np.ascontiguousarray(a, dtype=np.int32), int(a.shape[0])
+
+
+def _pair_call(call, b: DeviceBuild, what: str, Q: int, lists: bool, nids: Optional[int]) -> dict:
+    """One pair_policies entry point: ``call(cover, off, hist, total)``, then
+    the fetch of the id lists."""
+    cover = np.zeros(Q, dtype=np.int32)
+    off = np.zeros(Q + 1, dtype=np.int64) if lists else None
+    hist = None if nids is None else np.zeros(nids, dtype=np.int64)
+    total = c_int64(0)
+    b._chk(call(_ptr(cover), _ptr(off), _ptr(hist), byref(total)), what)
+    pol = None
+    if lists:
+        pol = np.zeros(int(total.value), dtype=np.int32)
+        b._chk(b.lib.kano_pair_policies_fetch(b.ctx, _ptr(pol)), "kano_pair_policies_fetch")
+    return dict(cover=cover, offsets=off, policies=pol, hist=hist)
+
+
+def pairs_from_lists(n_lists: int, nbits: int, soff: np.ndarray, slist: np.ndarray,
+                     allow_words: np.ndarray, pairs, device: int = 0, lists: bool = True,
+                     hist: bool = False, mode: Optional[int] = None) -> dict:
+    """pair_policies over explicit per-container policy lists and allow sets
+    (kano_pair_policies_lists): for every pair (list c, bit x) the ascending
+    ids of list c whose allow set holds x, as DeviceBuild.pair_policies
+    returns them.  An id repeated within a list counts once.  ``mode`` passes
+    a raw mode to the entry point."""
+    lib = nat.load()
+    b = DeviceBuild(None, device=device)
+    try:
+        aw = np.ascontiguousarray(allow_words, dtype=np.uint64)
+        P = aw.shape[0]
+        soff = np.ascontiguousarray(soff, dtype=np.int64)
+        slist = np.ascontiguousarray(slist, dtype=np.int32)
+        pr, Q = _as_pairs(pairs)
+        if mode is None:
+            mode = 0 if lists else 1
+        return _pair_call(
+            lambda *out: lib.kano_pair_policies_lists(b.ctx, int(n_lists), int(nbits), int(P),
+                                                      _ptr(soff), _ptr(slist), _ptr(aw), Q,
+                                                      _ptr(pr), int(mode), *out),
+            b, "kano_pair_policies_lists", Q, mode == 0, P if hist else None)
+    finally:
+        b.close()
 
 
 def shadow_from_lists(n_lists: int, nbits: int, soff: np.ndarray, slist: np.ndarray,

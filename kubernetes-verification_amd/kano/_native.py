@@ -57,6 +57,13 @@ SIGNATURES = {
     "kano_policy_impact": (c_int, [c_void_p, c_int, c_void_p, c_void_p, POINTER(c_int64)]),
     "kano_policy_impact_lists": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                                          c_void_p, c_int, c_void_p, c_void_p, POINTER(c_int64)]),
+    "kano_pair_policies": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p,
+                                   c_void_p, POINTER(c_int64)]),
+    "kano_pair_policies_fetch": (c_int, [c_void_p, c_void_p]),
+    "kano_pair_policies_lists": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                         c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p,
+                                         c_void_p, POINTER(c_int64)]),
+    "kano_pair_policies_time": (c_int, [c_void_p, POINTER(c_float)]),
     "kano_diff": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "kano_diff_pairs": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64,
                                 POINTER(c_int64), c_void_p]),

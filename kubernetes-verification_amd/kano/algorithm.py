@@ -351,6 +351,93 @@ def policy_redundant(matrix: ReachabilityMatrix, policies: List[Policy],
 
 
 # ---------------------------------------------------------------------------
+# Which policies make a pair reachable.  Not part of kano_py's algorithm.py.
+# Over the working sets of the matrix's current policies (matrix._policies:
+# after add_policies / remove_policies the updated list, current indices),
+#   pols(i, j)  = ascending indices p with i in select_p and j in allow_p
+#   cover(i, j) = len(pols(i, j))
+# computed on the device from the resident tables (kano_pair_policies), for
+# built and incrementally updated matrices alike.  Defined over the sets (a
+# policy appears once per pair; accumulated select_policies lists, quirk Q5,
+# do not change it).  The query speaks about the policies, not about bits
+# edited by hand: on a matrix without set-item / put_rows edits cover(i, j) > 0
+# iff M[i, j] = 1.  A matrix holding a row shard answers for the pairs whose i
+# it holds; the other pairs get cover 0.
+
+class PairPolicies(NamedTuple):
+    cover: np.ndarray          # int32, one per queried pair
+    offsets: np.ndarray        # int64 (Q + 1)
+    policies: np.ndarray       # int32: pair q's indices are policies[offsets[q]:offsets[q + 1]]
+
+    def of(self, q: int) -> List[int]:
+        """The ascending policy indices allowing queried pair q."""
+        q = int(q)
+        if not -len(self.cover) <= q < len(self.cover):
+            raise IndexError("pair index out of range")
+        q %= len(self.cover)
+        return self.policies[self.offsets[q]:self.offsets[q + 1]].tolist()
+
+
+def _pair_engine(matrix: ReachabilityMatrix, pairs):
+    """The engine, the checked (Q, 2) int32 pairs and the map from engine ids
+    to the indices of matrix._policies (None: they are equal)."""
+    from ._engine import _as_pairs
+    eng = _engine(matrix, whole=False)
+    ps = getattr(matrix, "_policies", None)
+    if ps is None:
+        raise ValueError("the matrix has no policies (a wrapped, copied, loaded, path or edge "
+                         "matrix holds rows only): pair_policies needs one from build_matrix")
+    pr, _ = _as_pairs(pairs)
+    n = matrix.container_size
+    if pr.size and (pr.min() < 0 or pr.max() >= n):
+        raise IndexError("bitarray index out of range")
+    eids = getattr(matrix, "_eids", None)
+    if eids is None or eids == list(range(len(ps))):
+        return eng, pr, None, len(ps)
+    back = np.full(max(eids) + 1 if eids else 0, -1, dtype=np.int32)
+    back[np.asarray(eids, dtype=np.int64)] = np.arange(len(eids), dtype=np.int32)
+    return eng, pr, (np.asarray(eids, dtype=np.int64), back), len(ps)
+
+
+def pair_policies(matrix: ReachabilityMatrix, pairs) -> PairPolicies:
+    """For every (i, j) of ``pairs`` (an (T, 2) int array as matrix_diff_pairs
+    returns it, or a list of tuples; any order, duplicates allowed) the
+    policies that select i and allow j (see PairPolicies)."""
+    eng, pr, ids, P = _pair_engine(matrix, pairs)
+    if P == 0:
+        z = np.zeros(pr.shape[0], np.int32)
+        return PairPolicies(z, np.zeros(pr.shape[0] + 1, np.int64), np.zeros(0, np.int32))
+    r = eng.pair_policies(pr, lists=True)
+    pol = r["policies"] if ids is None else ids[1][r["policies"]]
+    return PairPolicies(r["cover"], r["offsets"], pol)
+
+
+def pair_cover(matrix: ReachabilityMatrix, pairs) -> np.ndarray:
+    """cover(i, j) for every queried pair, int32 (the counts alone: no lists
+    on the device)."""
+    eng, pr, _, P = _pair_engine(matrix, pairs)
+    if P == 0:
+        return np.zeros(pr.shape[0], np.int32)
+    return eng.pair_policies(pr, lists=False)["cover"]
+
+
+def why_reachable(matrix: ReachabilityMatrix, i: int, j: int) -> List[int]:
+    """The ascending indices of the policies that select i and allow j."""
+    return pair_policies(matrix, [(int(i), int(j))]).of(0)
+
+
+def policy_blame(matrix: ReachabilityMatrix, pairs) -> np.ndarray:
+    """blame[p] = the number of queried pairs policy p allows (a pair repeated
+    in ``pairs`` counts each time): int64, one entry per current policy --
+    a set of violating pairs ranked by the policies behind them."""
+    eng, pr, ids, P = _pair_engine(matrix, pairs)
+    if P == 0:
+        return np.zeros(0, np.int64)
+    hist = eng.pair_policies(pr, lists=False, hist=True)["hist"]
+    return hist[:P].copy() if ids is None else hist[ids[0]]
+
+
+# ---------------------------------------------------------------------------
 # What a change adds and removes.  Not part of kano_py's algorithm.py.  For
 # two matrices over the same pods (and, for row shards, the same rows),
 #   added(i, j) = after[i, j] and not before[i, j]

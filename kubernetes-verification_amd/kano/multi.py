@@ -325,6 +325,29 @@ class MultiBuild:
         """essential[p]: the members' flags OR-ed."""
         return np.any([m.policy_essential() for m in self.members], axis=0)
 
+    def pair_policies(self, pairs, lists: bool = True, hist: bool = False) -> dict:
+        """DeviceBuild.pair_policies over all rows: the members' covers and
+        histograms summed (a pair counts on the member holding its i, the
+        others give 0), every pair's list taken from that member."""
+        nids = max(self.members[0].info()["P"], getattr(self, "_id_end", 0))
+        parts = [m.pair_policies(pairs, lists=lists, hist=hist, nids=nids)
+                 for m in self.members]
+        cover = np.sum([p["cover"] for p in parts], axis=0, dtype=np.int32)
+        out = dict(cover=cover, offsets=None, policies=None,
+                   hist=np.sum([p["hist"] for p in parts], axis=0, dtype=np.int64)
+                   if hist else None)
+        if lists:
+            off = np.zeros(cover.shape[0] + 1, dtype=np.int64)
+            np.cumsum(cover, out=off[1:])
+            pol = np.zeros(int(off[-1]), dtype=np.int32)
+            for p in parts:          # (entry k of a member's pair q goes to off[q] + k)
+                cnt = p["cover"]
+                at = np.arange(p["policies"].shape[0]) + np.repeat(off[:-1] - p["offsets"][:-1],
+                                                                   cnt)
+                pol[at] = p["policies"]
+            out.update(offsets=off, policies=pol)
+        return out
+
     # -- matrix access: owners --------------------------------------------
     def rows(self, r0: int, nrows: int, out: Optional[np.ndarray] = None) -> np.ndarray:
         if out is None:
@@ -416,6 +439,8 @@ class MultiBuild:
         self._chk(self.lib.kano_group_add_policies(
             self.g, int(so.shape[0] - 1), int(xv.shape[0]), _ptr(xv), _ptr(so), _ptr(sc),
             _ptr(sv), _ptr(ao), _ptr(ac), _ptr(av), byref(first)), "kano_group_add_policies")
+        # (engine ids in use: the build's and every added one, removed or not)
+        self._id_end = int(first.value) + int(so.shape[0] - 1)
         return int(first.value)
 
     def remove_policies(self, ids) -> None:
