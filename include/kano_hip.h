@@ -64,7 +64,9 @@ typedef struct kano_ctx kano_ctx;
 #define KANO_INFO_ROWS_CUS 14   /* CUs the last matrix write's stream may use  */
 #define KANO_INFO_HEAVY_SEL 15  /* sum of |S(c)| over the heavy classes       */
 #define KANO_INFO_HEAVY_KERNEL 16 /* 0 none, 1 k_heavy_mc_or, 2 k_heavy_mc_mfma (split K), 3 k_heavy_gemm */
-#define KANO_INFO_NSLOTS   17
+#define KANO_INFO_CLS_REUSED 17 /* builds on this context that reused the kept pod
+                                  classification (see kano_set_policies)        */
+#define KANO_INFO_NSLOTS   18
 
 /* Lifetime.  No reference counterpart: the reference keeps its state in
  * Python objects (kano_py/kano/model.py:167-169 ReachabilityMatrix.__init__). */
@@ -80,6 +82,15 @@ int  kano_set_stream(kano_ctx* ctx, void* hip_stream);   /* NULL = own stream */
 /* Inputs.  Replace the key-presence bitsets of build_matrix
  * (kano_py/kano/model.py:128-133) and the per-policy selector dicts it reads
  * through Policy.working_selector / working_allow (model.py:82-93, 142-147). */
+/* The pod classification (both sides' classes, member lists and
+ * representative values) depends only on the pod label table, each side's key
+ * columns (which label columns the policy terms name, not their values) and
+ * the row shard.  A successful build keeps it and later builds on the context
+ * reuse it (counted in KANO_INFO_CLS_REUSED).  It is classified again after:
+ * kano_set_pods, kano_set_expressions, a kano_add_policies that brings pod
+ * columns, a kano_set_shard with another range, a kano_set_policies whose
+ * terms name a different set of label columns on either side (an equal set
+ * keeps it), kano_shadow_lists and its kin, and any failed build. */
 int kano_set_pods(kano_ctx* ctx, int64_t n, int32_t ncols, const int32_t* pod_val);
 int kano_set_policies(kano_ctx* ctx, int64_t P,
                       const int64_t* sel_off, const int32_t* sel_col, const int32_t* sel_val,

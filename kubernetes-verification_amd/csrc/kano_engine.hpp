@@ -38,7 +38,12 @@ constexpr int MAX_CWW = 8192;   // column-chunk width in words (64 KB of LDS)
 // allowed-pod entry of S(c), so two 64-KB chunks cost 0.3 ms of row builds a
 // step, 8.4 -> 8.0 ms; C5 on one GPU neutral)
 constexpr int MAX_CWW_KNOB = 16384;
-constexpr int XCD_WRITE = 3;   // whole XCDs the write takes in the XCD split (96 CUs)
+// whole XCDs the write takes in the XCD split (96 CUs).  (With the kept
+// classification 4 was measured again on three devices: C3 0.301 -> 0.287 ms
+// on one, 0.304 -> 0.301 and 0.302 -> 0.298 (runs overlapping) on the others,
+// C4 no better -- the write gets shorter, the build's chain on four XCDs
+// longer; profiles/class_reuse_c3_ab.jsonl, tags xcdw3 / xcdw4)
+constexpr int XCD_WRITE = 3;
 constexpr long long XCD_MIN_BYTES = 1ll << 30;   // the split for writes of >= 1 GiB
 constexpr int HT_ROWS = 128;    // heavy rows per MFMA launch (HT = 4)
 // member rows per k_rows work item (each item rebuilds its class row: C3,
@@ -201,6 +206,20 @@ struct kano_ctx {
   int num_cus = 0, rows_cus = 0;   // the device's CUs; those of the last write's stream
 
   ClassSet rc, cc;           // row classes (selector keys), column classes (allow keys)
+  // The kept classification: both sides' classes are a function of the pod
+  // label table, each side's key columns and the shard range, none of which
+  // a policy edit or a repeated build changes.  A successful build leaves
+  // cls_valid set; the next build then skips the classification launches and
+  // host sync 1 and takes the class counts from cls_U.  Whatever changes an
+  // input (kano_set_pods, kano_set_expressions, an add with pod columns, a
+  // new shard range, a policy set with other keys, lists_setup) or a failed
+  // build clears it -- always with no prologue queued (they settle first).
+  // While it stands the members' buffers of RowsInputs are read-only and stay
+  // out of the input sets' exchange (swap_rows_ptrs).
+  bool cls_valid = false;
+  bool cls_reuse = false;    // the build (or prologue) in progress takes the kept classes
+  i64 cls_U[2] = {0, 0};     // the kept class counts: row side, column side
+  i64 cls_reused = 0;        // builds that took them (KANO_INFO_CLS_REUSED)
   SideMatch sm, am;          // selector side, allow side
   i64 UAW = 0, ldC = 0;      // words per class-level row (column classes)
   i64 nnz_sel = 0, nnz_alc = 0, nnz_alw = 0, heavy_count = 0, wi_total = 0, nflags = 0;
@@ -344,7 +363,8 @@ struct kano_ctx {
   // Pipelined calls (kano_set_pipeline): an asynchronously completing
   // kano_verify queues the next call's prologue -- the build's fills and
   // classification up to the member lists, which read only the resident
-  // inputs -- behind a gate kernel (k_gate) on the engine stream, into the
+  // inputs; under the kept classification the head fill alone (prime_kept)
+  // -- behind a gate kernel (k_gate) on the engine stream, into the
   // next input set and a private size-slot array.  The next kano_verify
   // rings the bell (a store to page-locked memory) instead of issuing those
   // launches; any other entry point rings it, waits, and puts both sets back
@@ -357,6 +377,7 @@ struct kano_ctx {
   bool prime_pre_marked = false;   // the prologue's member-list fill marked ev_pre
   bool prime_alist_valid = false;  // (restored by unprime)
   u64 prime_sig = 0;               // the prologue's class-count scan's host signal
+  bool prime_kept = false;         // the prologue took the kept classes (the head fill alone)
   u64* bell = nullptr;             // page-locked, coherent; bell_dev its device address
   u64* bell_dev = nullptr;
   u64 bell_seq = 0;

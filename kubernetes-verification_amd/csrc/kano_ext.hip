@@ -419,6 +419,7 @@ int kano_add_policies(kano_ctx* ctx, int64_t Pn, int32_t ncols_x, const int32_t*
     ctx->xv = grown;
   }
   ctx->inc_xcols += ncols_x;
+  if (ncols_x > 0) ctx->cls_valid = false;   // new pod columns: the next build classifies again
   // pod-level sets of the added policies (A x W words each side)
   const i64 A0 = ctx->inc_A, A1 = A0 + Pn;
   if (A1 > ctx->inc_acap) {

@@ -267,7 +267,8 @@ struct FillBatch {
     jobs.j[jobs.count++] = FillJob{static_cast<uint32_t*>(p), (i64)(bytes / 4), value};
     return 0;
   }
-  int run();
+  // mark: an event the launch's dispatch marks
+  int run(hipEvent_t mark = nullptr);
   // the pending jobs, for a launch that carries them (fill_item); none left
   FillJobs take() {
     FillJobs j = jobs;
@@ -292,19 +293,25 @@ int FillBatch::add(DBuf& b, size_t bytes, uint32_t value) {
   return 0;
 }
 
-int FillBatch::run() {
-  if (jobs.count == 0) return 0;
+int FillBatch::run(hipEvent_t mark) {
+  if (jobs.count == 0) {
+    if (mark) KCHK(hipEventRecord(mark, st ? st : ctx->stream));
+    return 0;
+  }
   i64 most = 0;
   for (int q = 0; q < jobs.count; ++q) most = std::max(most, jobs.j[q].words);
   const unsigned grid = (unsigned)std::max<i64>(1, std::min<i64>(2048, (most + TPB - 1) / TPB));
-  hipLaunchKernelGGL(k_fill_many, dim3(grid), dim3(TPB), 0, st ? st : ctx->stream, jobs);
+  launch_marked(k_fill_many, dim3(grid), dim3(TPB), 0, st ? st : ctx->stream, mark, jobs);
   KLAUNCH();
   jobs.count = 0;
   return 0;
 }
 
 // the two physical sets of k_rows' inputs exchanged (pointers only)
-void swap_rows_ptrs(kano_ctx* ctx) {
+// members: with the classes' member lists and column class ids -- left where
+// they are while the kept classification stands (nothing writes them, and
+// both sets read the same ones)
+void swap_rows_ptrs(kano_ctx* ctx, bool members) {
   RowsInputs& a = ctx->rin_alt;
   std::swap(ctx->wioff, a.wioff);
   std::swap(ctx->wicls, a.wicls);
@@ -314,11 +321,13 @@ void swap_rows_ptrs(kano_ctx* ctx) {
   std::swap(ctx->alist, a.alist);
   std::swap(ctx->alcoff, a.alcoff);
   std::swap(ctx->alc, a.alc);
-  std::swap(ctx->rc.moff, a.rmoff);
-  std::swap(ctx->rc.mem, a.rmem);
-  std::swap(ctx->cc.moff, a.cmoff);
-  std::swap(ctx->cc.mem, a.cmem);
-  std::swap(ctx->cc.cls, a.ccls);
+  if (members) {
+    std::swap(ctx->rc.moff, a.rmoff);
+    std::swap(ctx->rc.mem, a.rmem);
+    std::swap(ctx->cc.moff, a.cmoff);
+    std::swap(ctx->cc.mem, a.cmem);
+    std::swap(ctx->cc.cls, a.ccls);
+  }
   std::swap(ctx->hflag, a.hflag);
   std::swap(ctx->hlist, a.hlist);
   std::swap(ctx->Mc, a.Mc);
@@ -341,7 +350,7 @@ int unprime(kano_ctx* ctx) {
   KCHK(hipStreamSynchronize(ctx->stream));
   KCHK(hipStreamSynchronize(ctx->stream2));   // (its member lists run on stream2)
   std::swap(ctx->sizes, ctx->sizes_alt);
-  swap_rows_ptrs(ctx);
+  swap_rows_ptrs(ctx, !ctx->prime_kept);   // (as prime_next exchanged them)
   ctx->alist_valid = ctx->prime_alist_valid;
   return 0;
 }
@@ -395,7 +404,9 @@ int resolve_rows_time(kano_ctx* ctx, bool block = true) {
 // calls back, which last read it, has ended -- an event wait on the engine
 // stream, not on the host)
 int swap_rows_inputs(kano_ctx* ctx) {
-  swap_rows_ptrs(ctx);
+  // (a build that classifies again writes the other set's member lists: the
+  // write in flight keeps reading these, as without the kept classes)
+  swap_rows_ptrs(ctx, !ctx->cls_valid);
   ctx->alist_valid = false;
   // (usually long over: then no wait packet on the engine stream)
   if (ctx->rows_end_rec[ctx->rows_set]) {
@@ -831,6 +842,33 @@ int front_fills(kano_ctx* ctx, FillBatch& fb) {
 
 int select_engine_streams(kano_ctx* ctx);
 
+// The front end's buffers sized by the class counts, and their fills (the
+// join tables, |S(c)|, the rebuild cost, k_sel_place's cursors): carried by
+// k_cls_vals' launch, or part of the head fill under the kept classification
+int front_sized(kano_ctx* ctx, FillBatch& fb) {
+  const i64 P = ctx->P, Ur = ctx->rc.U;
+  KTRY(match_alloc(ctx, ctx->am, ctx->cc, fb));
+  KTRY(match_alloc(ctx, ctx->sm, ctx->rc, fb));
+  KTRY(dalloc(ctx, ctx->nca, sizeof(int32_t) * std::max<i64>(1, P)));
+  KTRY(dalloc(ctx, ctx->acnt, sizeof(int32_t) * std::max<i64>(1, P)));
+  KTRY(dalloc(ctx, ctx->alcoff, sizeof(i64) * (P + 1)));
+  KTRY(dalloc(ctx, ctx->aloff, sizeof(i64) * (P + 1)));
+  KTRY(dalloc(ctx, ctx->scnt, sizeof(int32_t) * std::max<i64>(1, Ur)));
+  KTRY(dalloc(ctx, ctx->cost, sizeof(u64) * std::max<i64>(1, Ur)));
+  KTRY(dalloc(ctx, ctx->wicnt, sizeof(int32_t) * std::max<i64>(1, Ur)));
+  KTRY(dalloc(ctx, ctx->hflag, sizeof(int32_t) * std::max<i64>(1, Ur)));
+  KTRY(dalloc(ctx, ctx->sq, sizeof(i64) * std::max<i64>(1, Ur)));
+  KTRY(dalloc(ctx, ctx->soffc, sizeof(i64) * (Ur + 1)));
+  KTRY(dalloc(ctx, ctx->wioff, sizeof(int32_t) * (Ur + 1)));
+  KTRY(dalloc(ctx, ctx->hoff, sizeof(int32_t) * (Ur + 1)));
+  KTRY(dalloc(ctx, ctx->pfoff, sizeof(i64) * (Ur + 1)));
+  KTRY(dalloc(ctx, ctx->scur, sizeof(int32_t) * std::max<i64>(1, Ur)));
+  KTRY(fb.add(ctx->scnt, sizeof(int32_t) * Ur, 0u));
+  KTRY(fb.add(ctx->cost, sizeof(u64) * Ur, 0u));
+  KTRY(fb.add(ctx->scur, sizeof(int32_t) * Ur, 0u));   // (k_sel_place's cursors)
+  return 0;
+}
+
 // The build's prologue, up to the member lists: it reads only the resident
 // inputs (the label tables), so a pipelined kano_verify queues it for the
 // next call behind the gate (prime_next)
@@ -840,6 +878,21 @@ int front_a(kano_ctx* ctx) {
   ctx->rc.m1 = ctx->r1;
   ctx->cc.m0 = 0;
   ctx->cc.m1 = ctx->n;
+  if (ctx->cls_reuse) {
+    // The kept classification: the class counts are the host's, so every fill
+    // up to the join goes into the one head launch -- the size slots and what
+    // k_cls_vals' launch carries otherwise; the classes' own tables stay as
+    // they are.  Its dispatch marks the side stream's fork (ev_pre), which
+    // the member counts' pass marks otherwise.
+    ctx->rc.U = ctx->cls_U[0];
+    ctx->cc.U = ctx->cls_U[1];
+    ctx->mlists_side = false;
+    FillBatch fb(ctx);
+    KTRY(dalloc(ctx, ctx->sizes, sizeof(u64) * SZ_SLOTS));
+    KTRY(fb.add(ctx->sizes, sizeof(u64) * SZ_SLOTS, 0u));
+    KTRY(front_sized(ctx, fb));
+    return fb.run(ctx->stream2 ? ctx->ev_pre : nullptr);
+  }
   {
     FillBatch fb(ctx);
     KTRY(front_fills(ctx, fb));
@@ -870,13 +923,21 @@ int do_front(kano_ctx* ctx, int path, bool primed = false) {
     ctx->rc.m1 = ctx->r1;
     ctx->cc.m0 = 0;
     ctx->cc.m1 = ctx->n;
-    ctx->sig_wait = ctx->prime_sig;   // (its class-count scan raises this signal)
+    // (its class-count scan raises this signal; with the kept classes the
+    // prologue has no scan and nothing below waits)
+    if (!ctx->cls_reuse) ctx->sig_wait = ctx->prime_sig;
   } else {
     KTRY(front_a(ctx));
   }
   ctx->pre_forked = ctx->stream2 != nullptr;
-  i64 u[2] = {0, 0};
-  KTRY(mirror_wait(ctx, SZ_UR, 2, u));
+  i64 u[2] = {ctx->cls_U[0], ctx->cls_U[1]};
+  if (ctx->cls_reuse) {
+    ctx->ht_wait++;   // (host sync 1 left out: the later waits keep their slots)
+  } else {
+    KTRY(mirror_wait(ctx, SZ_UR, 2, u));
+    ctx->cls_U[0] = u[0];
+    ctx->cls_U[1] = u[1];
+  }
   // an earlier matrix write's time, when it has ended (no wait: the
   // previous kano_verify's write may still run beside this build)
   KTRY(resolve_rows_time(ctx, false));
@@ -887,33 +948,13 @@ int do_front(kano_ctx* ctx, int path, bool primed = false) {
   const i64 P = ctx->P, Ur = ctx->rc.U, Ua = ctx->cc.U;
   ctx->UAW = (Ua + 63) / 64;
   ctx->ldC = std::max<i64>(2, (ctx->UAW + 1) & ~(i64)1);
-  FillJobs carried{};
-  {
+  if (!ctx->cls_reuse) {   // (else: allocated and filled by the head launch, front_a)
     FillBatch fb(ctx);
     KTRY(classify_alloc2(ctx, ctx->rc));
     KTRY(classify_alloc2(ctx, ctx->cc));
-    KTRY(match_alloc(ctx, ctx->am, ctx->cc, fb));
-    KTRY(match_alloc(ctx, ctx->sm, ctx->rc, fb));
-    KTRY(dalloc(ctx, ctx->nca, sizeof(int32_t) * std::max<i64>(1, P)));
-    KTRY(dalloc(ctx, ctx->acnt, sizeof(int32_t) * std::max<i64>(1, P)));
-    KTRY(dalloc(ctx, ctx->alcoff, sizeof(i64) * (P + 1)));
-    KTRY(dalloc(ctx, ctx->aloff, sizeof(i64) * (P + 1)));
-    KTRY(dalloc(ctx, ctx->scnt, sizeof(int32_t) * std::max<i64>(1, Ur)));
-    KTRY(dalloc(ctx, ctx->cost, sizeof(u64) * std::max<i64>(1, Ur)));
-    KTRY(dalloc(ctx, ctx->wicnt, sizeof(int32_t) * std::max<i64>(1, Ur)));
-    KTRY(dalloc(ctx, ctx->hflag, sizeof(int32_t) * std::max<i64>(1, Ur)));
-    KTRY(dalloc(ctx, ctx->sq, sizeof(i64) * std::max<i64>(1, Ur)));
-    KTRY(dalloc(ctx, ctx->soffc, sizeof(i64) * (Ur + 1)));
-    KTRY(dalloc(ctx, ctx->wioff, sizeof(int32_t) * (Ur + 1)));
-    KTRY(dalloc(ctx, ctx->hoff, sizeof(int32_t) * (Ur + 1)));
-    KTRY(dalloc(ctx, ctx->pfoff, sizeof(i64) * (Ur + 1)));
-    KTRY(dalloc(ctx, ctx->scur, sizeof(int32_t) * std::max<i64>(1, Ur)));
-    KTRY(fb.add(ctx->scnt, sizeof(int32_t) * Ur, 0u));
-    KTRY(fb.add(ctx->cost, sizeof(u64) * Ur, 0u));
-    KTRY(fb.add(ctx->scur, sizeof(int32_t) * Ur, 0u));   // (k_sel_place's cursors)
-    carried = fb.take();   // (carried by k_cls_vals' launch)
+    KTRY(front_sized(ctx, fb));
+    KTRY(classify_phase2b(ctx, fb.take()));   // (the fills carried by k_cls_vals' launch)
   }
-  KTRY(classify_phase2b(ctx, carried));
   KTRY(match_both(ctx));
   KTRY(stage_mark(ctx, 2, ctx->stream));
   // allowed classes / pods per policy, then |S(c)| and the rebuild cost
@@ -2552,6 +2593,7 @@ int kano_set_pods(kano_ctx* ctx, int64_t n, int32_t ncols, const int32_t* pod_va
     return fail(ctx, -EINVAL, "kano_set_pods: bad arguments");
   KCHK(hipSetDevice(ctx->device));
   KTRY(settle(ctx));
+  ctx->cls_valid = false;   // new labels: the kept classes describe the old ones
   ctx->n = n;
   ctx->W = (n + 63) / 64;
   ctx->ldM = std::max<i64>(LD_ALIGN, (ctx->W + LD_ALIGN - 1) / LD_ALIGN * LD_ALIGN);
@@ -2596,6 +2638,7 @@ int kano_set_expressions(kano_ctx* ctx, int32_t E, const int32_t* col, const int
   if (E == 0) return 0;
   KCHK(hipSetDevice(ctx->device));
   KTRY(settle(ctx));
+  ctx->cls_valid = false;   // the label table grows: classified again
   const i64 n = ctx->n, nc = ctx->ncols;
   for (int32_t e = 0; e < E; ++e) {
     if (col[e] >= nc || op[e] < 0 || op[e] > 3 || off[e + 1] < off[e])
@@ -2649,12 +2692,18 @@ static int prepare_side(kano_ctx* ctx, i64 P, const int64_t* off, const int32_t*
     if (col[t] < 0 || col[t] >= ctx->ncols) return fail(ctx, -EINVAL, "term column out of range");
     slot[col[t]] = 0;
   }
+  const std::vector<int32_t> keys_before(cs.keys);
+  const int packed_before = cs.packed, tbits_before = cs.tbits;
   cs.keys.clear();
   for (int32_t c = 0; c < ctx->ncols; ++c)
     if (slot[c] == 0) {
       slot[c] = (int32_t)cs.keys.size();
       cs.keys.push_back(c);
     }
+  // the kept classification stands only while this side hashes the same
+  // columns in the same form (an equal key set keeps it: a policy edit that
+  // names no new label key)
+  const bool same_keys = cs.keys == keys_before;
   cs.KS = (int)cs.keys.size();
   // keys_d = [columns | bits]; packed when the bits sum to at most 63
   std::vector<int32_t> kd(cs.keys);
@@ -2667,6 +2716,7 @@ static int prepare_side(kano_ctx* ctx, i64 P, const int64_t* off, const int32_t*
   // too, so its pods meet in LDS instead of CAS-ing one global slot)
   cs.packed = (tb <= 63 && ctx->cls_packed) ? 1 : 0;
   cs.tbits = tb;
+  if (!same_keys || cs.packed != packed_before || cs.tbits != tbits_before) ctx->cls_valid = false;
   KTRY(dalloc(ctx, cs.keys_d, sizeof(int32_t) * std::max<size_t>(1, kd.size())));
   if (cs.KS > 0)   // uploaded once per policy set, not per build
     KCHK(hipMemcpy(cs.keys_d.p, kd.data(), sizeof(int32_t) * kd.size(), hipMemcpyHostToDevice));
@@ -2807,6 +2857,8 @@ int kano_set_shard(kano_ctx* ctx, int64_t row_begin, int64_t row_end) {
   if (!ctx->have_pods || row_begin < 0 || row_end < row_begin || row_end > ctx->n)
     return fail(ctx, -EINVAL, "kano_set_shard: bad row range");
   KTRY(settle(ctx));
+  // (the row classes cover the shard's pods: another range, other classes)
+  if (row_begin != ctx->r0 || row_end != ctx->r1) ctx->cls_valid = false;
   ctx->r0 = row_begin;
   ctx->r1 = row_end;
   ctx->built = false;
@@ -2853,6 +2905,11 @@ int build_impl(kano_ctx* ctx, int path, bool rows_now, bool defer_cols = false,
   if (!ctx->have_pods || !ctx->have_pols) return fail(ctx, -EINVAL, "kano_build: inputs not set");
   if (path < 0 || path > 2) return fail(ctx, -EINVAL, "kano_build: unknown path");
   KCHK(hipSetDevice(ctx->device));
+  // the kept classification is this build's when it stands (a consumed
+  // prologue was queued by the same state: whatever clears the mark unprimes
+  // first); cleared until the build has succeeded, so a failed one drops it
+  ctx->cls_reuse = consume ? ctx->prime_kept : ctx->cls_valid;
+  ctx->cls_valid = false;
   ctx->built = false;
   ctx->rows_deferred = false;
   ctx->lists_mode = false;
@@ -2885,6 +2942,9 @@ int build_impl(kano_ctx* ctx, int path, bool rows_now, bool defer_cols = false,
   KTRY(stage_mark(ctx, 4, ctx->stream));
   ctx->cols_valid = true;
   ctx->built = true;
+  ctx->cls_valid = true;
+  if (ctx->cls_reuse) ++ctx->cls_reused;
+  ctx->cls_reuse = false;
   // a build discards earlier incremental updates and edits
   ctx->inc_A = 0;
   ctx->inc_xcols = 0;
@@ -2928,6 +2988,7 @@ int kano_info(kano_ctx* ctx, int64_t* out) {
   out[KANO_INFO_HEAVY_KERNEL] = ctx->heavy_kernel;
   out[KANO_INFO_WORK_ITEMS] = ctx->wi_total;
   out[KANO_INFO_ROWS_KERNEL] = ctx->rows_kernel;
+  out[KANO_INFO_CLS_REUSED] = ctx->cls_reused;
   return 0;
 }
 
@@ -3442,6 +3503,7 @@ int lists_setup(kano_ctx* ctx, const char* what, int64_t n_lists, int64_t nbits,
   ctx->conflict_total = -1;   // (the tables below replace what it was computed from)
   // every list is its own row class; every pod its own column class
   ctx->built = false;
+  ctx->cls_valid = false;   // (rc.cls, rc.mcnt and the class counts are the lists' below)
   ctx->lists_mode = true;
   ctx->n = nbits;
   ctx->W = (nbits + 63) / 64;
@@ -4269,6 +4331,10 @@ int prime_next(kano_ctx* ctx) {
   if (ctx->primed || !ctx->bell || ctx->stage_timing) return 0;
   KTRY(dalloc(ctx, ctx->sizes_alt, sizeof(u64) * SZ_SLOTS));
   ctx->prime_alist_valid = ctx->alist_valid;
+  // (with the kept classes the prologue is the head fill alone, and no scan
+  // of it raises a host signal: do_front then waits for none)
+  ctx->prime_kept = ctx->cls_valid;
+  ctx->cls_reuse = ctx->cls_valid;
   KTRY(swap_rows_inputs(ctx));
   std::swap(ctx->sizes, ctx->sizes_alt);
   ctx->primed = true;

@@ -116,6 +116,17 @@ class DeviceBuild:
             pass
 
     # -- inputs / build -------------------------------------------------
+    def set_policies(self, t: Tables) -> None:
+        """kano_set_policies alone: another policy list over the pods already
+        uploaded (t's pod columns must be the uploaded ones).  The engine keeps
+        its pod classification when the new terms name the same label keys."""
+        self.tables = t
+        arrs = [np.ascontiguousarray(a, dtype=d) for a, d in (
+            (t.sel_off, np.int64), (t.sel_col, np.int32), (t.sel_val, np.int32),
+            (t.alw_off, np.int64), (t.alw_col, np.int32), (t.alw_val, np.int32))]
+        self._chk(self.lib.kano_set_policies(self.ctx, t.P, *[_ptr(a) for a in arrs]),
+                  "kano_set_policies")
+
     def upload(self, t: Tables) -> None:
         self.tables = t
         self.row_span = None          # kano_set_pods resets the engine to every row
@@ -127,11 +138,7 @@ class DeviceBuild:
                 (t.expr_val, np.int32))]
             self._chk(self.lib.kano_set_expressions(self.ctx, len(ex[0]), *[_ptr(a) for a in ex]),
                       "kano_set_expressions")
-        arrs = [np.ascontiguousarray(a, dtype=d) for a, d in (
-            (t.sel_off, np.int64), (t.sel_col, np.int32), (t.sel_val, np.int32),
-            (t.alw_off, np.int64), (t.alw_col, np.int32), (t.alw_val, np.int32))]
-        self._chk(self.lib.kano_set_policies(self.ctx, t.P, *[_ptr(a) for a in arrs]),
-                  "kano_set_policies")
+        self.set_policies(t)
 
     def set_rows(self, r0: int, r1: int) -> None:
         self._chk(self.lib.kano_set_shard(self.ctx, int(r0), int(r1)), "kano_set_shard")
