@@ -345,6 +345,56 @@ int kano_group_counts(kano_ctx* ctx, const int32_t* gsrc /* n */, int32_t Gs,
  * copies, in ms; recorded under KANO_TUNE=timing=1, else 0. */
 int kano_group_counts_time(kano_ctx* ctx, float* ms);
 
+/* hop_distance / path_witness: shortest paths over the matrix, read as a graph
+ * with an edge i -> j iff M[i,j] = 1.  For a source s,
+ *   dist(s, t) = the least k >= 1 such that a walk of k edges leads from s to
+ *                t, -1 if there is none (or none within max_hops; 0 = no bound)
+ * -- k starts at 1, as the closure's "paths of any length >= 1": dist(s, s) is
+ * 1 with a self-loop, else the shortest cycle through s, else -1.  With
+ * L_0 = {s}, V_0 = {} and L_k = (OR of row(u), u in L_{k-1}) \ V_{k-1},
+ * V_k = V_{k-1} | L_k: dist(s, v) = k iff v in L_k.  So
+ * kano_path(hops = k)[s,t] = 1 iff 1 <= dist(s,t) <= k, and the closure's bit
+ * iff dist(s,t) >= 1.  Bits at positions >= n of a row's last word
+ * (kano_put_rows copies them unmasked) are no edges.
+ * The canonical shortest path of a pair with d = dist(s, t) >= 1 is
+ * [s, t_1, .., t_{d-1}, t] with t_d = t and t_{k-1} = the smallest u in
+ * L_{k-1} with M[u, t_k] = 1: d + 1 nodes, every step an edge, unique.
+ * Works on every whole matrix a context holds (built, edited, updated,
+ * loaded, path, edge): the matrix is present and pending work waited for, as
+ * for kano_group_counts; a breadth-first search runs level by level for a
+ * batch of up to 64 sources at once, in device buffers that are the call's own
+ * (the matrix and every stored result are unchanged).  The host reads the
+ * batch's frontier sizes after every level: one round trip a level, so a
+ * chain-shaped graph of depth d costs d of them.  Exact integers.
+ * kano_hops: dist[k * n + v] = dist(sources[k], v) for S sources (duplicates
+ * allowed); info[4] (nullable) = the levels run (the largest finite distance
+ * found), the rows OR-ed (frontier pods over all levels and sources), the
+ * batches, the pods reached (entries of dist that are >= 1).
+ * kano_hop_pairs: dist[q] = dist(pairs[2q], pairs[2q+1]) for Q pairs in any
+ * order, duplicates allowed; one search per distinct source, which stops once
+ * all of that source's targets have a distance.  mode 0: distances alone;
+ * mode 1: also the canonical paths -- pair q's path has dist[q] + 1 nodes (0
+ * when dist[q] < 0) at the prefix sum of those lengths over the pairs before
+ * it, *total (nullable) = their sum; kano_hop_pairs_fetch copies the nodes
+ * out (-EINVAL after mode 0, after an error and before any call).
+ * -EINVAL: a NULL context or array, S / Q < 0, max_hops < 0, an unknown mode,
+ * a context holding only a row shard (the search needs every row);
+ * -ERANGE: a source or target outside [0, n); -ENOTSUP: S * n > 268,435,456
+ * (2^28 distances: ask in slices); -ENOMEM (with a message): a device buffer
+ * could not be allocated.  n = 0, S = 0 or Q = 0 give empty results and launch
+ * nothing.  The context stays usable after every error. */
+int kano_hops(kano_ctx* ctx, int64_t S, const int32_t* sources, int32_t max_hops,
+              int32_t* dist /* S*n */, int64_t* info /* 4, or NULL */);
+int kano_hop_pairs(kano_ctx* ctx, int64_t Q, const int32_t* pairs /* 2*Q */, int32_t max_hops,
+                   int mode /* 0 distances, 1 + paths */, int32_t* dist /* Q */,
+                   int64_t* total /* path nodes, or NULL */);
+int kano_hop_pairs_fetch(kano_ctx* ctx, int32_t* nodes /* total */);
+/* The last kano_hops / kano_hop_pairs' device time in ms, summed over its
+ * batches: from a batch's first fill to its last kernel, the waits for the
+ * host's per-level reads included, the result copies not; recorded under
+ * KANO_TUNE=timing=1, else 0. */
+int kano_hops_time(kano_ctx* ctx, float* ms);
+
 /* The whole verification pass in one call (the sequence kano_py's
  * sample/example.py and tests/test_basic.py run: build_matrix, then
  * all_reachable, all_isolated, user_crosscheck, system_isolation and

@@ -293,6 +293,12 @@ struct kano_ctx {
   // group_reachability (kano_group_counts): its device buffers are the
   // call's own; only the time stays
   float group_ms = 0.f;       // timing=1: the last call's fills + kernels (kano_group_counts_time)
+  // hop_distance / path_witness (kano_hops / kano_hop_pairs): the device
+  // buffers are the call's own; the paths of the last kano_hop_pairs wait in
+  // host memory for kano_hop_pairs_fetch (hop_total < 0: none to fetch)
+  std::vector<int32_t> hop_nodes;
+  i64 hop_total = -1;
+  float hops_ms = 0.f;        // timing=1: the last call's searches, level waits included (kano_hops_time)
   // policy_shadow count-only (kano_verify with shadow_cap < 0): the grouped
   // count (k_shg_*) instead of the pair-by-pair flags
   bool vs_count_only = false;

@@ -8,6 +8,7 @@
 #include "kano_inc.hpp"
 #include "kano_k8s.hpp"
 #include "kano_path.hpp"
+#include "kano_hops.hpp"
 
 using namespace kano_eng;
 
@@ -1046,6 +1047,360 @@ int kano_group_counts(kano_ctx* ctx, const int32_t* gsrc, int32_t Gs, const int3
 int kano_group_counts_time(kano_ctx* ctx, float* ms) {
   if (!ctx || !ms) return -EINVAL;
   *ms = ctx->group_ms;
+  return 0;
+}
+
+}  // extern "C"
+
+// ===========================================================================
+// hop_distance / path_witness: breadth-first search over the resident matrix
+// (k_hops_*, kano_hops.hpp), a batch of sources at once.
+// ===========================================================================
+namespace {
+
+constexpr i64 HOPS_MAX_CELLS = 1ll << 28;     // S * n of one kano_hops call (1 GiB of dist)
+constexpr i64 HOPS_BUDGET = 1ll << 30;        // bytes of per-source device state of one batch
+constexpr i64 HOPS_MAX_BATCH = 64;            // sources of one batch at most
+constexpr i64 HOPS_TARGET_WAVES = 16384;      // expand items (waves) a level aims at
+
+// what a call accumulates over its batches (kano_hops' info)
+struct HopsStats {
+  i64 levels = 0, rows_ored = 0, batches = 0, reached = 0;
+};
+
+// the call's own buffers: per source dist and the frontier list (n int32
+// each), visited | next | target mask (W words each); the batch's sources,
+// counters and target counts; the counters' page-locked landing buffer
+struct HopsBufs {
+  DBuf dist, list, bits, small, items, gath, nodes;
+  int32_t* pin = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  i64 B = 0;
+  float ms = 0.f;
+};
+
+void hops_free(kano_ctx* ctx, HopsBufs& h, int rc) {
+  if (rc) (void)hipStreamSynchronize(ctx->stream);   // nothing in flight on the temporaries
+  for (DBuf* b : {&h.dist, &h.list, &h.bits, &h.small, &h.items, &h.gath, &h.nodes}) dfree(*b);
+  if (h.pin) (void)hipHostFree(h.pin);
+  h.pin = nullptr;
+  for (hipEvent_t& e : h.ev) {
+    if (e) (void)hipEventDestroy(e);
+    e = nullptr;
+  }
+}
+
+// the shared preamble: arguments, the matrix present and complete, every row held
+int hops_prepare(kano_ctx* ctx, const char* what, int32_t max_hops) {
+  const std::string w(what);
+  if (max_hops < 0) return fail(ctx, -EINVAL, w + ": max_hops < 0");
+  KTRY(ensure_matrix(ctx));
+  if (ctx->r0 != 0 || ctx->r1 != ctx->n)
+    return fail(ctx, -EINVAL, w + ": the context holds rows [" + std::to_string(ctx->r0) + ", " +
+                                  std::to_string(ctx->r1) + ") of " + std::to_string(ctx->n) +
+                                  ": a search needs every row");
+  return sync(ctx);
+}
+
+int hops_alloc(kano_ctx* ctx, HopsBufs& h, i64 nsrc, bool targets) {
+  const i64 n = ctx->n, W = ctx->W;
+  const i64 per = 8 * n + 24 * W + 64;
+  h.B = std::max<i64>(1, std::min<i64>({HOPS_MAX_BATCH, HOPS_BUDGET / per, nsrc}));
+  KTRY(dalloc(ctx, h.dist, sizeof(int32_t) * (size_t)(h.B * n)));
+  KTRY(dalloc(ctx, h.list, sizeof(int32_t) * (size_t)(h.B * n)));
+  KTRY(dalloc(ctx, h.bits, sizeof(u64) * (size_t)((targets ? 3 : 2) * h.B * W)));
+  KTRY(dalloc(ctx, h.small, sizeof(int32_t) * (size_t)(5 * h.B)));
+  KCHK(hipHostMalloc(reinterpret_cast<void**>(&h.pin), sizeof(int32_t) * (size_t)(3 * h.B),
+                     hipHostMallocDefault));
+  if (ctx->stage_timing) {
+    KCHK(hipEventCreate(&h.ev[0]));
+    KCHK(hipEventCreate(&h.ev[1]));
+  }
+  return 0;
+}
+
+// One batch: the searches of B sources (src, host) level by level.  tmask /
+// ntgt (host; both or neither): per source its targets' bit row and their
+// number -- a source stops once all of them have a distance.  On return the
+// batch's dist arrays are resident in h.dist and the stream is idle; the
+// timing events stay open for the caller's kernels (hops_batch_end).
+int hops_batch(kano_ctx* ctx, HopsBufs& h, i64 B, const int32_t* src, int32_t max_hops,
+               const u64* tmask, const int32_t* ntgt, HopsStats& st) {
+  const i64 n = ctx->n, W = ctx->W;
+  int32_t* small = P_<int32_t>(h.small);
+  int32_t* src_d = small;
+  int32_t* cnts_d = small + h.B;          // 3 B entries, laid out for this batch's B
+  int32_t* ntgt_d = small + 4 * h.B;
+  u64* visited = P_<u64>(h.bits);
+  u64* next = visited + B * W;
+  u64* tmask_d = tmask ? next + B * W : nullptr;
+  KCHK(hipMemcpyAsync(src_d, src, sizeof(int32_t) * B, hipMemcpyHostToDevice, ctx->stream));
+  if (tmask) {
+    KCHK(hipMemcpyAsync(ntgt_d, ntgt, sizeof(int32_t) * B, hipMemcpyHostToDevice, ctx->stream));
+    KCHK(hipMemcpyAsync(tmask_d, tmask, sizeof(u64) * B * W, hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (h.ev[0]) KCHK(hipEventRecord(h.ev[0], ctx->stream));
+  const i64 cells = std::max(B * n, 2 * B * W);
+  hipLaunchKernelGGL(k_hops_init, dim3(std::min<i64>(4096, nblk(cells))), dim3(TPB), 0,
+                     ctx->stream, P_<int32_t>(h.dist), visited, P_<int32_t>(h.list), cnts_d, src_d,
+                     n, W, (int)B);
+  KLAUNCH();
+  std::vector<int32_t> cnt((size_t)B, 1);
+  std::vector<char> live((size_t)B, 1);
+  const i64 nch = (W + HOPS_CW - 1) / HOPS_CW;
+  for (i64 k = 1; max_hops == 0 || k <= max_hops; ++k) {
+    i64 nlive = 0, maxcnt = 0, sum = 0;
+    for (i64 b = 0; b < B; ++b)
+      if (live[b]) {
+        ++nlive;
+        maxcnt = std::max<i64>(maxcnt, cnt[b]);
+        sum += cnt[b];
+      }
+    if (nlive == 0) break;
+    if (k > 0x7fffffff) return fail(ctx, -ENOTSUP, "kano_hops: level count overflow");
+    st.rows_ored += sum;
+    // slices of the frontier: enough waves to fill the device, each OR-ing
+    // at least HOPS_MIN_SLICE rows before its atomics
+    const i64 slice = std::max<i64>(HOPS_MIN_SLICE,
+                                    (maxcnt * nch * nlive + HOPS_TARGET_WAVES - 1) /
+                                        HOPS_TARGET_WAVES);
+    const i64 nsl = nblk((maxcnt + slice - 1) / slice, TPB / 64);
+    hipLaunchKernelGGL(k_hops_expand, dim3((unsigned)nch, (unsigned)nsl, (unsigned)B), dim3(TPB),
+                       0, ctx->stream, P_<u64>(ctx->M), ctx->ldM, n, W, P_<int32_t>(h.list),
+                       cnts_d, tmask ? ntgt_d : (const int32_t*)nullptr, (int)B, (int)k,
+                       (int)slice, next);
+    KLAUNCH();
+    hipLaunchKernelGGL(k_hops_finish, dim3((unsigned)nblk(W), (unsigned)B), dim3(TPB), 0,
+                       ctx->stream, n, W, visited, next, (const u64*)tmask_d, P_<int32_t>(h.dist),
+                       P_<int32_t>(h.list), cnts_d, tmask ? ntgt_d : (const int32_t*)nullptr,
+                       (int)B, (int)k);
+    KLAUNCH();
+    KCHK(hipMemcpyAsync(h.pin, cnts_d, sizeof(int32_t) * 3 * B, hipMemcpyDeviceToHost,
+                        ctx->stream));
+    KTRY(sync(ctx));
+    const int32_t* now = h.pin + (k & 1) * B;
+    const int32_t* hit = h.pin + 2 * B;
+    for (i64 b = 0; b < B; ++b) {
+      if (!live[b]) continue;
+      cnt[b] = now[b];
+      if (cnt[b] > 0) {
+        st.reached += cnt[b];
+        st.levels = std::max(st.levels, k);
+      }
+      live[b] = cnt[b] > 0 && !(ntgt && hit[b] >= ntgt[b]);
+    }
+  }
+  st.batches += 1;
+  return 0;
+}
+
+// closes the batch's timing (after the caller's gather / witness kernels)
+int hops_batch_end(kano_ctx* ctx, HopsBufs& h) {
+  if (!h.ev[0]) return 0;
+  KCHK(hipEventRecord(h.ev[1], ctx->stream));
+  KCHK(hipEventSynchronize(h.ev[1]));
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, h.ev[0], h.ev[1]);
+  h.ms += ms;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kano_hops(kano_ctx* ctx, int64_t S, const int32_t* sources, int32_t max_hops, int32_t* dist,
+              int64_t* info) {
+  if (!ctx) return -EINVAL;
+  if (S < 0 || (S > 0 && (!sources || !dist)))
+    return fail(ctx, -EINVAL, "kano_hops: S < 0, or sources or dist is NULL");
+  KTRY(hops_prepare(ctx, "kano_hops", max_hops));
+  const i64 n = ctx->n;
+  for (i64 k = 0; k < S; ++k)
+    if (sources[k] < 0 || sources[k] >= n)
+      return fail(ctx, -ERANGE, "kano_hops: source " + std::to_string(sources[k]) +
+                                    " outside [0, " + std::to_string(n) + ")");
+  if (n > 0 && S > HOPS_MAX_CELLS / n)
+    return fail(ctx, -ENOTSUP, "kano_hops: S * n = " + std::to_string(S * n) + " beyond " +
+                                   std::to_string(HOPS_MAX_CELLS) + " (ask in slices)");
+  if (info) std::memset(info, 0, sizeof(int64_t) * 4);
+  ctx->hops_ms = 0.f;
+  if (n == 0 || S == 0) return 0;
+  HopsBufs h;
+  HopsStats st;
+  auto run = [&]() -> int {
+    KTRY(hops_alloc(ctx, h, S, false));
+    for (i64 s0 = 0; s0 < S; s0 += h.B) {
+      const i64 B = std::min(h.B, S - s0);
+      KTRY(hops_batch(ctx, h, B, sources + s0, max_hops, nullptr, nullptr, st));
+      KTRY(hops_batch_end(ctx, h));
+      KCHK(hipMemcpyAsync(dist + s0 * n, h.dist.p, sizeof(int32_t) * (size_t)(B * n),
+                          hipMemcpyDeviceToHost, ctx->stream));
+      KTRY(sync(ctx));
+    }
+    return 0;
+  };
+  const int rc = run();
+  ctx->hops_ms = h.ms;
+  hops_free(ctx, h, rc);
+  if (rc) return rc;
+  if (info) {
+    info[0] = st.levels;
+    info[1] = st.rows_ored;
+    info[2] = st.batches;
+    info[3] = st.reached;
+  }
+  return 0;
+}
+
+int kano_hop_pairs(kano_ctx* ctx, int64_t Q, const int32_t* pairs, int32_t max_hops, int mode,
+                   int32_t* dist, int64_t* total) {
+  if (!ctx) return -EINVAL;
+  if (total) *total = 0;
+  ctx->hop_total = -1;
+  ctx->hop_nodes.clear();
+  if (Q < 0 || (Q > 0 && (!pairs || !dist)))
+    return fail(ctx, -EINVAL, "kano_hop_pairs: Q < 0, or pairs or dist is NULL");
+  if (mode != 0 && mode != 1) return fail(ctx, -EINVAL, "kano_hop_pairs: unknown mode");
+  KTRY(hops_prepare(ctx, "kano_hop_pairs", max_hops));
+  const i64 n = ctx->n, W = ctx->W;
+  for (i64 q = 0; q < 2 * Q; ++q)
+    if (pairs[q] < 0 || pairs[q] >= n)
+      return fail(ctx, -ERANGE, "kano_hop_pairs: pod " + std::to_string(pairs[q]) +
+                                    " outside [0, " + std::to_string(n) + ")");
+  ctx->hops_ms = 0.f;
+  if (mode == 1) ctx->hop_total = 0;
+  if (Q == 0 || n == 0) return 0;
+
+  // the pairs by source: one search per distinct source, whatever its targets
+  std::vector<i64> order((size_t)Q);
+  for (i64 q = 0; q < Q; ++q) order[q] = q;
+  std::stable_sort(order.begin(), order.end(),
+                   [&](i64 x, i64 y) { return pairs[2 * x] < pairs[2 * y]; });
+  std::vector<int32_t> srcs;          // distinct, ascending
+  std::vector<i64> first;             // srcs[k]'s pairs are order[first[k] .. first[k + 1])
+  for (i64 p = 0; p < Q; ++p)
+    if (p == 0 || pairs[2 * order[p]] != srcs.back()) {
+      srcs.push_back(pairs[2 * order[p]]);
+      first.push_back(p);
+    }
+  first.push_back(Q);
+  const i64 S = (i64)srcs.size();
+
+  HopsBufs h;
+  HopsStats st;
+  std::vector<int32_t> sorted_nodes;  // the paths in `order`'s order
+  std::vector<int32_t> dsort((size_t)Q);
+  auto run = [&]() -> int {
+    KTRY(hops_alloc(ctx, h, S, true));
+    std::vector<u64> tmask((size_t)(h.B * W));
+    std::vector<int32_t> ntgt((size_t)h.B);
+    std::vector<int2> items;
+    std::vector<HopsWitness> wit;
+    for (i64 s0 = 0; s0 < S; s0 += h.B) {
+      const i64 B = std::min(h.B, S - s0);
+      const i64 p0 = first[s0], p1 = first[s0 + B], np = p1 - p0;
+      std::fill(tmask.begin(), tmask.begin() + B * W, 0ull);
+      items.resize((size_t)np);
+      for (i64 b = 0; b < B; ++b) {
+        int32_t distinct = 0;
+        for (i64 p = first[s0 + b]; p < first[s0 + b + 1]; ++p) {
+          const int32_t t = pairs[2 * order[p] + 1];
+          u64& word = tmask[(size_t)(b * W + (t >> 6))];
+          if (!(word >> (t & 63) & 1ull)) ++distinct;
+          word |= 1ull << (t & 63);
+          items[(size_t)(p - p0)] = make_int2((int)b, t);
+        }
+        ntgt[b] = distinct;
+      }
+      KTRY(dalloc(ctx, h.items, sizeof(int2) * (size_t)np));
+      KTRY(dalloc(ctx, h.gath, sizeof(int32_t) * (size_t)np));
+      KTRY(hops_batch(ctx, h, B, srcs.data() + s0, max_hops, tmask.data(), ntgt.data(), st));
+      KCHK(hipMemcpyAsync(h.items.p, items.data(), sizeof(int2) * (size_t)np,
+                          hipMemcpyHostToDevice, ctx->stream));
+      hipLaunchKernelGGL(k_hops_gather, dim3(nblk(np)), dim3(TPB), 0, ctx->stream,
+                         P_<int32_t>(h.dist), n, P_<int2>(h.items), np, P_<int32_t>(h.gath));
+      KLAUNCH();
+      KCHK(hipMemcpyAsync(dsort.data() + p0, h.gath.p, sizeof(int32_t) * (size_t)np,
+                          hipMemcpyDeviceToHost, ctx->stream));
+      KTRY(sync(ctx));
+      if (mode == 1) {
+        // the witnesses while the batch's dist arrays are resident
+        wit.clear();
+        i64 off = 0;
+        for (i64 p = p0; p < p1; ++p) {
+          const int32_t d = dsort[p];
+          if (d < 1) continue;
+          wit.push_back(HopsWitness{items[(size_t)(p - p0)].x, items[(size_t)(p - p0)].y, d,
+                                    pairs[2 * order[p]], off});
+          off += (i64)d + 1;
+        }
+        if (!wit.empty()) {
+          if (wit.size() > (size_t)0x7fffffff)
+            return fail(ctx, -ENOTSUP, "kano_hop_pairs: too many paths in one batch");
+          KTRY(dalloc(ctx, h.items, sizeof(HopsWitness) * wit.size()));
+          KTRY(dalloc(ctx, h.nodes, sizeof(int32_t) * (size_t)off));
+          KCHK(hipMemcpyAsync(h.items.p, wit.data(), sizeof(HopsWitness) * wit.size(),
+                              hipMemcpyHostToDevice, ctx->stream));
+          hipLaunchKernelGGL(k_hops_witness, dim3((unsigned)wit.size()), dim3(TPB), 0, ctx->stream,
+                             P_<u64>(ctx->M), ctx->ldM, n, P_<int32_t>(h.dist),
+                             P_<HopsWitness>(h.items), P_<int32_t>(h.nodes));
+          KLAUNCH();
+          KTRY(hops_batch_end(ctx, h));
+          const size_t at = sorted_nodes.size();
+          sorted_nodes.resize(at + (size_t)off);
+          KCHK(hipMemcpyAsync(sorted_nodes.data() + at, h.nodes.p, sizeof(int32_t) * (size_t)off,
+                              hipMemcpyDeviceToHost, ctx->stream));
+          KTRY(sync(ctx));
+        } else {
+          KTRY(hops_batch_end(ctx, h));
+        }
+      } else {
+        KTRY(hops_batch_end(ctx, h));
+      }
+    }
+    return 0;
+  };
+  const int rc = run();
+  ctx->hops_ms = h.ms;
+  hops_free(ctx, h, rc);
+  if (rc) {
+    ctx->hop_total = -1;
+    return rc;
+  }
+  for (i64 p = 0; p < Q; ++p) dist[order[p]] = dsort[p];
+  if (mode == 1) {
+    // pair q's path at the prefix sum of dist + 1 over the pairs before it
+    std::vector<i64> offq((size_t)Q + 1, 0);
+    for (i64 q = 0; q < Q; ++q) offq[q + 1] = offq[q] + (dist[q] >= 1 ? (i64)dist[q] + 1 : 0);
+    ctx->hop_nodes.assign((size_t)offq[Q], 0);
+    i64 at = 0;
+    for (i64 p = 0; p < Q; ++p) {
+      const i64 q = order[p], len = offq[q + 1] - offq[q];
+      if (len) std::memcpy(ctx->hop_nodes.data() + offq[q], sorted_nodes.data() + at,
+                           sizeof(int32_t) * (size_t)len);
+      at += len;
+    }
+    ctx->hop_total = offq[Q];
+    if (total) *total = offq[Q];
+  }
+  return 0;
+}
+
+int kano_hop_pairs_fetch(kano_ctx* ctx, int32_t* nodes) {
+  if (!ctx) return -EINVAL;
+  if (ctx->hop_total < 0)
+    return fail(ctx, -EINVAL, "kano_hop_pairs_fetch: no paths (call kano_hop_pairs with mode 1)");
+  if (ctx->hop_total > 0) {
+    if (!nodes) return fail(ctx, -EINVAL, "kano_hop_pairs_fetch: nodes is NULL");
+    std::memcpy(nodes, ctx->hop_nodes.data(), sizeof(int32_t) * (size_t)ctx->hop_total);
+  }
+  return 0;
+}
+
+int kano_hops_time(kano_ctx* ctx, float* ms) {
+  if (!ctx || !ms) return -EINVAL;
+  *ms = ctx->hops_ms;
   return 0;
 }
 

@@ -747,6 +747,47 @@ class DeviceBuild:
         self._chk(self.lib.kano_group_counts_time(self.ctx, byref(ms)), "kano_group_counts_time")
         return float(ms.value)
 
+    # -- hop_distance / path_witness (kano_hops / kano_hop_pairs) -----------
+    HOPS_INFO = ("levels", "rows_ored", "batches", "reached")
+
+    def hops(self, sources, max_hops: int = 0) -> dict:
+        """Shortest distances from every pod of ``sources`` over the matrix
+        read as a graph: ``dist`` (int32, (S, n); -1: no walk of >= 1 edges,
+        or none within ``max_hops`` > 0) and ``info`` (levels run, rows OR-ed,
+        batches, pods reached).  The context must hold every row."""
+        src = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
+        n = self.info()["N"]
+        dist = np.empty((src.shape[0], n), dtype=np.int32)
+        info = np.zeros(4, dtype=np.int64)
+        self._chk(self.lib.kano_hops(self.ctx, int(src.shape[0]), _ptr(src), int(max_hops),
+                                     _ptr(dist), _ptr(info)), "kano_hops")
+        return dict(dist=dist, info={k: int(v) for k, v in zip(self.HOPS_INFO, info)})
+
+    def hop_pairs(self, pairs, max_hops: int = 0, paths: bool = False) -> dict:
+        """``dist`` (int32, Q) of every (source, target) pair of ``pairs``
+        ((Q, 2) int32, any order, duplicates allowed) and, with ``paths``, the
+        canonical shortest paths: pair q's nodes are
+        nodes[offsets[q]:offsets[q + 1]] (dist[q] + 1 of them, none when
+        dist[q] < 0); else ``offsets`` and ``nodes`` are None."""
+        pr, Q = _as_pairs(pairs)
+        dist = np.empty(Q, dtype=np.int32)
+        total = c_int64(0)
+        self._chk(self.lib.kano_hop_pairs(self.ctx, Q, _ptr(pr), int(max_hops), int(bool(paths)),
+                                          _ptr(dist), byref(total)), "kano_hop_pairs")
+        if not paths:
+            return dict(dist=dist, offsets=None, nodes=None)
+        off = np.zeros(Q + 1, dtype=np.int64)
+        np.cumsum(np.where(dist >= 1, dist.astype(np.int64) + 1, 0), out=off[1:])
+        nodes = np.zeros(int(total.value), dtype=np.int32)
+        self._chk(self.lib.kano_hop_pairs_fetch(self.ctx, _ptr(nodes)), "kano_hop_pairs_fetch")
+        return dict(dist=dist, offsets=off, nodes=nodes)
+
+    def hops_time(self) -> float:
+        """The last hops / hop_pairs' device time (ms; KANO_TUNE=timing=1)."""
+        ms = ctypes.c_float(0.0)
+        self._chk(self.lib.kano_hops_time(self.ctx, byref(ms)), "kano_hops_time")
+        return float(ms.value)
+
     def rows_timing(self, reset: bool = False) -> dict:
         """k_rows launch times (HIP events) since the last reset: sum, count,
         min, max (ms); waits for the context's work."""

@@ -72,6 +72,11 @@ SIGNATURES = {
     "kano_group_counts": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p,
                                   c_void_p]),
     "kano_group_counts_time": (c_int, [c_void_p, POINTER(c_float)]),
+    "kano_hops": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p]),
+    "kano_hop_pairs": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int, c_void_p,
+                               POINTER(c_int64)]),
+    "kano_hop_pairs_fetch": (c_int, [c_void_p, c_void_p]),
+    "kano_hops_time": (c_int, [c_void_p, POINTER(c_float)]),
     "kano_verify": (c_int, [c_void_p, c_int, c_void_p, c_int32, c_int64, c_void_p, c_void_p,
                             c_void_p, c_int64, POINTER(c_int64)]),
     "kano_verify_shard": (c_int, [c_void_p, c_int, c_void_p, c_int32, c_int64, c_int, c_void_p]),

@@ -627,3 +627,82 @@ def transitive_closure(matrix: ReachabilityMatrix, mode: str = "auto") -> Reacha
     """M+: pairs joined by a path of any length >= 1 (the fixpoint of the
     path rule applied to itself)."""
     return _path_matrix(matrix, 0, mode)
+
+
+# ---------------------------------------------------------------------------
+# Through which pods, and in how many hops.  Not part of kano_py's
+# algorithm.py.  two_hop / k_hop / transitive_closure answer with a matrix of
+# bits; these answer with the distance and the route.  With an edge i -> j iff
+# M[i, j] = 1,
+#   dist(s, t) = the least k >= 1 such that a walk of k edges leads from s to
+#                t, -1 if there is none (or none within max_hops; 0 = no bound)
+# (k starts at 1 as the closure's paths do: dist(s, s) is 1 with a self-loop,
+# else the shortest cycle through s, else -1), so
+#   k_hop(M, k)[s, t] = 1  iff  1 <= dist(s, t) <= k,
+#   transitive_closure(M)[s, t] = 1  iff  dist(s, t) >= 1.
+# The canonical shortest path of a pair with d = dist(s, t) >= 1 is
+# [s, t_1, .., t_{d-1}, t], built backwards from t_d = t with t_{k-1} = the
+# smallest pod at distance k - 1 from s that has an edge to t_k.  Computed on
+# the device by a breadth-first search over the matrix itself (kano_hops /
+# kano_hop_pairs), so it holds for built, updated, edited, loaded, path and
+# edge matrices alike.  The search reads every row: a matrix holding a row
+# shard raises.  One host round trip per level: a chain of depth d costs d.
+
+class HopPaths(NamedTuple):
+    dist: np.ndarray           # int32, one per queried pair (-1: unreachable)
+    offsets: np.ndarray        # int64 (Q + 1)
+    nodes: np.ndarray          # int32: pair q's path is nodes[offsets[q]:offsets[q + 1]]
+
+    def of(self, q: int) -> List[int]:
+        """The canonical shortest path of queried pair q ([] when unreachable)."""
+        q = int(q)
+        if not -len(self.dist) <= q < len(self.dist):
+            raise IndexError("pair index out of range")
+        q %= len(self.dist)
+        return self.nodes[self.offsets[q]:self.offsets[q + 1]].tolist()
+
+
+def _hop_bound(max_hops) -> int:
+    if int(max_hops) < 0:
+        raise ValueError("max_hops must be >= 0 (0: no bound)")
+    return int(max_hops)
+
+
+def _hop_pairs(matrix: ReachabilityMatrix, pairs, max_hops, paths: bool) -> dict:
+    from ._engine import _as_pairs
+    eng = _engine(matrix, whole=True)
+    pr, _ = _as_pairs(pairs)
+    if pr.size and (pr.min() < 0 or pr.max() >= matrix.container_size):
+        raise IndexError("bitarray index out of range")
+    return eng.hop_pairs(pr, _hop_bound(max_hops), paths=paths)
+
+
+def hop_levels(matrix: ReachabilityMatrix, sources, max_hops: int = 0) -> np.ndarray:
+    """dist(s, v) for every source s of ``sources`` and every pod v: int32
+    (len(sources), n); an ``int`` source gives (n,)."""
+    eng = _engine(matrix, whole=True)
+    one = isinstance(sources, (int, np.integer))
+    src = np.asarray([sources] if one else list(sources), dtype=np.int64).reshape(-1)
+    if src.size and (src.min() < 0 or src.max() >= matrix.container_size):
+        raise IndexError("bitarray index out of range")
+    dist = eng.hops(src.astype(np.int32), _hop_bound(max_hops))["dist"]
+    return dist[0] if one else dist
+
+
+def hop_distance(matrix: ReachabilityMatrix, pairs, max_hops: int = 0) -> np.ndarray:
+    """dist(i, j) for every (i, j) of ``pairs`` (a (Q, 2) int array or a list
+    of tuples; any order, duplicates allowed): int32 (Q,)."""
+    return _hop_pairs(matrix, pairs, max_hops, False)["dist"]
+
+
+def path_witnesses(matrix: ReachabilityMatrix, pairs, max_hops: int = 0) -> HopPaths:
+    """The distance and the canonical shortest path of every queried pair
+    (see HopPaths)."""
+    r = _hop_pairs(matrix, pairs, max_hops, True)
+    return HopPaths(r["dist"], r["offsets"], r["nodes"])
+
+
+def path_witness(matrix: ReachabilityMatrix, i: int, j: int, max_hops: int = 0) -> List[int]:
+    """The canonical shortest path from i to j as a list of pod indices
+    ([] when j is unreachable from i, or not within max_hops)."""
+    return path_witnesses(matrix, [(int(i), int(j))], max_hops).of(0)

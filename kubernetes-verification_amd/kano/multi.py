@@ -537,6 +537,24 @@ class MultiBuild:
         return dict(counts=counts,
                     row_counts=np.concatenate([p["row_counts"] for p in parts]) if rows else None)
 
+    # -- hop_distance / path_witness ----------------------------------------------
+    def _hops_member(self) -> DeviceBuild:
+        """A search ORs the rows of every pod it reaches: it needs the whole
+        matrix on one device (no per-level exchange across row shards)."""
+        if len(self.members) != 1:
+            raise ValueError(f"hop queries need the whole matrix on one device: this group "
+                             f"holds it in {len(self.members)} row shards")
+        return self.members[0]
+
+    def hops(self, sources, max_hops: int = 0) -> dict:
+        return self._hops_member().hops(sources, max_hops)
+
+    def hop_pairs(self, pairs, max_hops: int = 0, paths: bool = False) -> dict:
+        return self._hops_member().hop_pairs(pairs, max_hops, paths)
+
+    def hops_time(self) -> float:
+        return self._hops_member().hops_time()
+
     # -- measurement ------------------------------------------------------------
     def exchange_timing(self, enable: Optional[bool] = None, reset: bool = False) -> dict:
         """The verify exchange's time on member 0's stream (HIP events around
