@@ -395,6 +395,63 @@ int kano_hop_pairs_fetch(kano_ctx* ctx, int32_t* nodes /* total */);
  * KANO_TUNE=timing=1, else 0. */
 int kano_hops_time(kano_ctx* ctx, float* ms);
 
+/* check_intents: what the cluster is supposed to do, checked against the
+ * matrix.  Intent k is a source set src[k] and a destination set dst[k] (W
+ * words each, bit j of a set in word j >> 6 at position j & 63, the sets free
+ * to overlap each other and those of other intents) and flags[k]: bit 0 set
+ * = an allow intent (every source must reach every destination), clear = a
+ * deny intent (no source may reach a destination); bit 1 set = the pairs
+ * (i, i) are considered too.  With S = the pods of src[k] among the rows
+ * r0..r1 this context holds, D = the pods of dst[k] and
+ *   C = {(i, j) : i in S, j in D, and i != j unless bit 1 is set},
+ * out[6k ..] (int64) =
+ *   n_src = |S|, n_dst = |D|, pairs = |C|,
+ *   reachable   = #{(i, j) in C : M[i,j] = 1},
+ *   violations  = reachable for a deny intent, pairs - reachable for an allow
+ *                 intent,
+ *   bad_sources = #{i in S : some (i, j) in C is a violation},
+ * and witness[2k ..] (int32) = the violating (i, j) smallest by i, then j, or
+ * (-1, -1) without one.  Set bits at positions >= n, and bits at positions
+ * >= n of a row's last word (kano_put_rows copies them unmasked), are nobody.
+ * Exact integers.  Works on every matrix a context holds (built, edited,
+ * updated, loaded, path, edge, row shard): the matrix is present (as for
+ * kano_get_rows), pending work is waited for, and the passes over the
+ * resident rows run on the context's stream in device buffers that are the
+ * call's own: both set arrays, the sources' row lists (at most 1 GiB a pass
+ * over the intents) and 40 bytes an intent.  The call reads 8 * W bytes of
+ * the matrix per source of every intent: 8 * W * (sum of n_src) in all, a row
+ * that several intents share once for each.  K == 0, n == 0 or no local rows
+ * give zeros and (-1, -1) and launch nothing.  Over row shards every field
+ * but n_dst adds up, and the witness is the smallest of the shards'.
+ * kano_intent_pairs: one intent's violations as (i, j) int32 pairs with
+ * global indices, ascending by i and then j.  Self-contained: the call counts
+ * first.  *count is always set (0 on an argument error); pairs NULL asks for
+ * the count alone.  With pairs given and count > limit the call returns
+ * -ENOSPC and writes no pair.
+ * -EINVAL: a NULL context or array (kano_intents: with K > 0), K < 0,
+ * limit < 0, a NULL count, flag bits other than 0 and 1;
+ * -ENOTSUP: K * W > 134,217,728 words (2^27, 1 GiB a side: ask in slices of
+ * K); the sum over the intents of n_src * W > 274,877,906,944 row words (2^38,
+ * 2 TiB of reads -- a guard against occupying the device for minutes by
+ * accident, known on the host before anything is launched: narrow the
+ * selectors or split the call); kano_intent_pairs past 4,194,304 source rows;
+ * -ENOMEM (with a message): a device buffer could not be allocated.  No error
+ * writes a result.  The context stays usable after every error.  The matrix,
+ * the class tables and every stored check result (column words, crosscheck
+ * words, shadow and conflict pairs, impact) are unchanged; a call between
+ * pipelined kano_verify steps leaves the next step's results unchanged. */
+int kano_intents(kano_ctx* ctx, int64_t K, const uint64_t* src /* K*W */,
+                 const uint64_t* dst /* K*W */,
+                 const int32_t* flags /* K: bit 0 = allow kind, bit 1 = keep self pairs */,
+                 int64_t* out /* K*6: n_src, n_dst, pairs, reachable, violations, bad_sources */,
+                 int32_t* witness /* K*2 */);
+int kano_intent_pairs(kano_ctx* ctx, const uint64_t* src /* W */, const uint64_t* dst /* W */,
+                      int32_t flags, int64_t limit, int64_t* count,
+                      int32_t* pairs /* 2*limit, or NULL: count only */);
+/* The last kano_intents' device time, its kernels without the copies, in ms;
+ * recorded under KANO_TUNE=timing=1, else 0. */
+int kano_intents_time(kano_ctx* ctx, float* ms);
+
 /* The whole verification pass in one call (the sequence kano_py's
  * sample/example.py and tests/test_basic.py run: build_matrix, then
  * all_reachable, all_isolated, user_crosscheck, system_isolation and

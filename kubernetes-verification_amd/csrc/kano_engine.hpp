@@ -299,6 +299,9 @@ struct kano_ctx {
   std::vector<int32_t> hop_nodes;
   i64 hop_total = -1;
   float hops_ms = 0.f;        // timing=1: the last call's searches, level waits included (kano_hops_time)
+  // check_intents (kano_intents / kano_intent_pairs): the device buffers are
+  // the call's own; only the time stays
+  float intents_ms = 0.f;     // timing=1: the last kano_intents' kernels (kano_intents_time)
   // policy_shadow count-only (kano_verify with shadow_cap < 0): the grouped
   // count (k_shg_*) instead of the pair-by-pair flags
   bool vs_count_only = false;

@@ -9,6 +9,7 @@
 #include "kano_k8s.hpp"
 #include "kano_path.hpp"
 #include "kano_hops.hpp"
+#include "kano_intents.hpp"
 
 using namespace kano_eng;
 
@@ -1401,6 +1402,269 @@ int kano_hop_pairs_fetch(kano_ctx* ctx, int32_t* nodes) {
 int kano_hops_time(kano_ctx* ctx, float* ms) {
   if (!ctx || !ms) return -EINVAL;
   *ms = ctx->hops_ms;
+  return 0;
+}
+
+}  // extern "C"
+
+// ===========================================================================
+// check_intents: user-declared allow / deny intents against the resident
+// matrix (k_intent_*, kano_intents.hpp), every intent of a call at once.
+// ===========================================================================
+namespace {
+
+constexpr i64 INTENT_MAX_WORDS = 1ll << 27;       // K * W of one call (1 GiB a side)
+constexpr i64 INTENT_MAX_ROW_WORDS = 1ll << 38;   // sum of |S_k| * W of one call (2 TiB of reads)
+constexpr i64 INTENT_LIST_BUDGET = 1ll << 30;     // bytes of source row lists of one pass
+
+// the set bits of s (W words) among the rows [r0, r1)
+i64 intent_held_count(const u64* s, i64 r0, i64 r1) {
+  i64 c = 0;
+  for (i64 w = r0 >> 6; w <= (r1 - 1) >> 6; ++w) {
+    u64 v = s[w];
+    if (w == r0 >> 6) v &= ~0ull << (r0 & 63);
+    if (w == (r1 - 1) >> 6 && (r1 & 63)) v &= (1ull << (r1 & 63)) - 1ull;
+    c += __builtin_popcountll(v);
+  }
+  return c;
+}
+
+// intent descriptors for counts ns[0 .. K): rows of an item, item and list offsets
+void intent_descs(const i64* ns, const int32_t* flags, i64 K, std::vector<IntentDesc>& d) {
+  d.resize((size_t)K + 1);
+  i64 loff = 0, ioff = 0;
+  for (i64 k = 0; k < K; ++k) {
+    i64 run = std::max<i64>(INTENT_R, (ns[k] + INTENT_MAX_ITEMS - 1) / INTENT_MAX_ITEMS);
+    run = (run + INTENT_RB - 1) / INTENT_RB * INTENT_RB;
+    d[k] = IntentDesc{loff, ioff, (int32_t)run, flags[k]};
+    loff += ns[k];
+    ioff += (ns[k] + run - 1) / run;
+  }
+  d[K] = IntentDesc{loff, ioff, 0, 0};
+}
+
+unsigned intent_grid(const kano_ctx* ctx, i64 waves) {
+  const i64 cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
+  return (unsigned)std::max<i64>(1, std::min<i64>(nblk(waves, TPB / 64), cus * 8));
+}
+
+}  // namespace
+
+extern "C" {
+
+int kano_intents(kano_ctx* ctx, int64_t K, const uint64_t* src, const uint64_t* dst,
+                 const int32_t* flags, int64_t* out, int32_t* witness) {
+  if (!ctx) return -EINVAL;
+  if (K < 0) return fail(ctx, -EINVAL, "kano_intents: K < 0");
+  if (K > 0 && (!src || !dst || !flags || !out || !witness))
+    return fail(ctx, -EINVAL, "kano_intents: src, dst, flags, out or witness is NULL");
+  KTRY(ensure_matrix(ctx));
+  const i64 n = ctx->n, W = ctx->W, r0 = ctx->r0, r1 = ctx->r1;
+  const i64 rl = std::max<i64>(0, rows_local(ctx));
+  if (W > 0 && K > INTENT_MAX_WORDS / W)
+    return fail(ctx, -ENOTSUP, "kano_intents: K * W = " + std::to_string(K) + " * " +
+                                   std::to_string(W) + " words beyond " +
+                                   std::to_string(INTENT_MAX_WORDS) + " (ask in slices of K)");
+  for (i64 k = 0; k < K; ++k)
+    if (flags[k] & ~(INTENT_ALLOW | INTENT_SELF))
+      return fail(ctx, -EINVAL, "kano_intents: intent " + std::to_string(k) +
+                                    " has unknown flag bits");
+  const bool empty = K == 0 || n == 0 || W == 0 || rl == 0;
+  // the held sources of every intent: the row reads of the call, known before
+  // anything is launched
+  const u64* S = reinterpret_cast<const u64*>(src);
+  std::vector<i64> ns((size_t)K, 0);
+  i64 rows_total = 0;
+  if (!empty)
+    for (i64 k = 0; k < K; ++k) {
+      ns[k] = intent_held_count(S + k * W, r0, r1);
+      rows_total += ns[k];
+    }
+  if (!empty && rows_total > INTENT_MAX_ROW_WORDS / W)
+    return fail(ctx, -ENOTSUP, "kano_intents: " + std::to_string(rows_total) +
+                                   " source rows of " + std::to_string(W) + " words beyond " +
+                                   std::to_string(INTENT_MAX_ROW_WORDS) +
+                                   " row words in one call (narrow the selectors or split the call)");
+  for (i64 k = 0; k < K; ++k) {
+    std::memset(out + 6 * k, 0, sizeof(int64_t) * 6);
+    witness[2 * k] = witness[2 * k + 1] = -1;
+  }
+  ctx->intents_ms = 0.f;
+  KTRY(sync(ctx));
+  if (empty) return 0;
+
+  // passes over the intents: the row lists of one pass within the budget
+  std::vector<i64> pass{0};
+  {
+    const i64 cap = INTENT_LIST_BUDGET / (i64)sizeof(int32_t);
+    i64 rows = 0;
+    for (i64 k = 0; k < K; ++k) {
+      if (rows > 0 && rows + ns[k] > cap) {
+        pass.push_back(k);
+        rows = 0;
+      }
+      rows += ns[k];
+    }
+    pass.push_back(K);
+  }
+  const i64 npass = (i64)pass.size() - 1;
+  std::vector<IntentDesc> descs, one;
+  std::vector<i64> dbase((size_t)npass);
+  i64 max_rows = 0;
+  for (i64 p = 0; p < npass; ++p) {
+    const i64 k0 = pass[p], Kp = pass[p + 1] - k0;
+    intent_descs(ns.data() + k0, flags + k0, Kp, one);
+    dbase[p] = (i64)descs.size();
+    descs.insert(descs.end(), one.begin(), one.end());
+    max_rows = std::max(max_rows, one[Kp].loff);
+  }
+
+  // the call's own buffers
+  DBuf sd, list, dd, res;
+  std::vector<u64> hres((size_t)K * INTENT_RES);
+  auto run = [&]() -> int {
+    const size_t b_set = sizeof(u64) * (size_t)K * (size_t)W;
+    KTRY(dalloc(ctx, sd, 2 * b_set));
+    KTRY(dalloc(ctx, list, sizeof(int32_t) * (size_t)max_rows));
+    KTRY(dalloc(ctx, dd, sizeof(IntentDesc) * descs.size()));
+    KTRY(dalloc(ctx, res, sizeof(u64) * hres.size()));
+    u64* src_d = P_<u64>(sd);
+    u64* dst_d = src_d + (size_t)K * (size_t)W;
+    KCHK(hipMemcpyAsync(src_d, src, b_set, hipMemcpyHostToDevice, ctx->stream));
+    KCHK(hipMemcpyAsync(dst_d, dst, b_set, hipMemcpyHostToDevice, ctx->stream));
+    KCHK(hipMemcpyAsync(dd.p, descs.data(), sizeof(IntentDesc) * descs.size(),
+                        hipMemcpyHostToDevice, ctx->stream));
+    // timing=1: the call's device time (the kernels, no copy)
+    hipEvent_t tev[2] = {nullptr, nullptr};
+    if (ctx->stage_timing) {
+      KCHK(hipEventCreate(&tev[0]));
+      KCHK(hipEventCreate(&tev[1]));
+      KCHK(hipEventRecord(tev[0], ctx->stream));
+    }
+    for (i64 p = 0; p < npass; ++p) {
+      const i64 k0 = pass[p], Kp = pass[p + 1] - k0;
+      const IntentDesc* de = P_<IntentDesc>(dd) + dbase[p];
+      const i64 nitems = descs[(size_t)(dbase[p] + Kp)].ioff;
+      u64* rp = P_<u64>(res) + k0 * INTENT_RES;
+      hipLaunchKernelGGL(k_intent_lists, dim3(intent_grid(ctx, Kp)), dim3(TPB), 0, ctx->stream,
+                         src_d + k0 * W, dst_d + k0 * W, W, n, r0, r1, de, Kp,
+                         P_<int32_t>(list), rp);
+      KLAUNCH();
+      if (nitems == 0) continue;
+      hipLaunchKernelGGL(k_intent_rows, dim3(intent_grid(ctx, nitems)), dim3(TPB), 0, ctx->stream,
+                         P_<u64>(ctx->M), ctx->ldM, r0, rl, W, (const u64*)(dst_d + k0 * W), de, Kp,
+                         nitems, (const int32_t*)P_<int32_t>(list), rp);
+      KLAUNCH();
+    }
+    if (tev[0]) {
+      KCHK(hipEventRecord(tev[1], ctx->stream));
+      KCHK(hipEventSynchronize(tev[1]));
+      (void)hipEventElapsedTime(&ctx->intents_ms, tev[0], tev[1]);
+      (void)hipEventDestroy(tev[0]);
+      (void)hipEventDestroy(tev[1]);
+    }
+    KCHK(hipMemcpyAsync(hres.data(), res.p, sizeof(u64) * hres.size(), hipMemcpyDeviceToHost,
+                        ctx->stream));
+    return sync(ctx);
+  };
+  const int rc = run();
+  if (rc) (void)hipStreamSynchronize(ctx->stream);   // nothing in flight on the temporaries
+  for (DBuf* b : {&sd, &list, &dd, &res}) dfree(*b);
+  if (rc) return rc;
+  for (i64 k = 0; k < K; ++k) {
+    const u64* h = hres.data() + k * INTENT_RES;
+    int64_t* o = out + 6 * k;
+    const i64 nd = (i64)h[0], reach = (i64)h[2];
+    const i64 pairs = ns[k] * nd - ((flags[k] & INTENT_SELF) ? 0 : (i64)h[1]);
+    o[0] = ns[k];
+    o[1] = nd;
+    o[2] = pairs;
+    o[3] = reach;
+    o[4] = (flags[k] & INTENT_ALLOW) ? pairs - reach : reach;
+    o[5] = (i64)h[3];
+    if (h[4] != ~0ull) {
+      witness[2 * k] = (int32_t)(h[4] >> 32);
+      witness[2 * k + 1] = (int32_t)(h[4] & 0xffffffffull);
+    }
+  }
+  return 0;
+}
+
+int kano_intent_pairs(kano_ctx* ctx, const uint64_t* src, const uint64_t* dst, int32_t flags,
+                      int64_t limit, int64_t* count, int32_t* pairs) {
+  if (!ctx) return -EINVAL;
+  if (!count) return fail(ctx, -EINVAL, "kano_intent_pairs: count is NULL");
+  *count = 0;
+  if (!src || !dst) return fail(ctx, -EINVAL, "kano_intent_pairs: src or dst is NULL");
+  if (flags & ~(INTENT_ALLOW | INTENT_SELF))
+    return fail(ctx, -EINVAL, "kano_intent_pairs: unknown flag bits");
+  if (limit < 0) return fail(ctx, -EINVAL, "kano_intent_pairs: limit < 0");
+  KTRY(ensure_matrix(ctx));
+  KTRY(sync(ctx));
+  const i64 n = ctx->n, W = ctx->W, r0 = ctx->r0, r1 = ctx->r1;
+  const i64 rl = rows_local(ctx);
+  if (n == 0 || W == 0 || rl <= 0) return 0;
+  const i64 ns = intent_held_count(reinterpret_cast<const u64*>(src), r0, r1);
+  if (ns == 0) return 0;
+  if (ns > (i64)DIFF_SCAN_TILES * SCAN_TILE)
+    return fail(ctx, -ENOTSUP, "kano_intent_pairs: more than " +
+                                   std::to_string((i64)DIFF_SCAN_TILES * SCAN_TILE) +
+                                   " source rows in one call");
+  std::vector<IntentDesc> desc;
+  intent_descs(&ns, &flags, 1, desc);
+  DBuf sd, list, dd, res, cnt, off, outb;
+  auto run = [&]() -> int {
+    KTRY(dalloc(ctx, sd, sizeof(u64) * 2 * (size_t)W));
+    KTRY(dalloc(ctx, list, sizeof(int32_t) * (size_t)ns));
+    KTRY(dalloc(ctx, dd, sizeof(IntentDesc) * 2));
+    KTRY(dalloc(ctx, res, sizeof(u64) * INTENT_RES));
+    KTRY(dalloc(ctx, cnt, sizeof(int32_t) * (size_t)ns));
+    KTRY(dalloc(ctx, off, sizeof(i64) * (size_t)(ns + 1 + 2 * DIFF_SCAN_TILES + 1)));
+    u64* src_d = P_<u64>(sd);
+    u64* dst_d = src_d + W;
+    KCHK(hipMemcpyAsync(src_d, src, sizeof(u64) * W, hipMemcpyHostToDevice, ctx->stream));
+    KCHK(hipMemcpyAsync(dst_d, dst, sizeof(u64) * W, hipMemcpyHostToDevice, ctx->stream));
+    KCHK(hipMemcpyAsync(dd.p, desc.data(), sizeof(IntentDesc) * 2, hipMemcpyHostToDevice,
+                        ctx->stream));
+    hipLaunchKernelGGL(k_intent_lists, dim3(1), dim3(TPB), 0, ctx->stream, src_d, dst_d, W, n, r0,
+                       r1, (const IntentDesc*)P_<IntentDesc>(dd), (i64)1, P_<int32_t>(list),
+                       P_<u64>(res));
+    KLAUNCH();
+    // pass one: the violations of every source row, then their offsets
+    hipLaunchKernelGGL(k_intent_row_counts, dim3(intent_grid(ctx, ns)), dim3(TPB), 0, ctx->stream,
+                       P_<u64>(ctx->M), ctx->ldM, r0, rl, W, (const u64*)dst_d, (int)flags,
+                       (const int32_t*)P_<int32_t>(list), ns, P_<int32_t>(cnt));
+    KLAUNCH();
+    i64* offp = P_<i64>(off);
+    KTRY(diff_offsets_launch(ctx, P_<int32_t>(cnt), ns, offp + ns + 1, offp));
+    i64 total = 0;
+    KCHK(hipMemcpyAsync(&total, offp + ns, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
+    KTRY(sync(ctx));
+    *count = total;
+    if (!pairs || total == 0) return 0;
+    if (total > limit)
+      return fail(ctx, -ENOSPC, "kano_intent_pairs: " + std::to_string(total) +
+                                    " pairs, room for " + std::to_string(limit));
+    // pass two: the pairs in order
+    KTRY(dalloc(ctx, outb, sizeof(int32_t) * 2 * (size_t)total));
+    hipLaunchKernelGGL(k_intent_emit, dim3(intent_grid(ctx, ns)), dim3(TPB), 0, ctx->stream,
+                       P_<u64>(ctx->M), ctx->ldM, r0, rl, W, (const u64*)dst_d, (int)flags,
+                       (const int32_t*)P_<int32_t>(list), ns, (const i64*)offp, total,
+                       P_<int32_t>(outb));
+    KLAUNCH();
+    KCHK(hipMemcpyAsync(pairs, outb.p, sizeof(int32_t) * 2 * (size_t)total, hipMemcpyDeviceToHost,
+                        ctx->stream));
+    return sync(ctx);
+  };
+  const int rc = run();
+  if (rc) (void)hipStreamSynchronize(ctx->stream);   // nothing in flight on the temporaries
+  for (DBuf* b : {&sd, &list, &dd, &res, &cnt, &off, &outb}) dfree(*b);
+  return rc;
+}
+
+int kano_intents_time(kano_ctx* ctx, float* ms) {
+  if (!ctx || !ms) return -EINVAL;
+  *ms = ctx->intents_ms;
   return 0;
 }
 

@@ -788,6 +788,72 @@ class DeviceBuild:
         self._chk(self.lib.kano_hops_time(self.ctx, byref(ms)), "kano_hops_time")
         return float(ms.value)
 
+    # -- check_intents (kano_intents / kano_intent_pairs) -------------------
+    INTENT_ALLOW, INTENT_SELF = 1, 2     # flag bits
+    INTENT_RUN_ROWS = 16                 # csrc/kano_intents.hpp INTENT_R: rows of a work item at least
+    INTENT_MAX_WORDS = 1 << 27           # K * W words of one kano_intents call
+    INTENT_FIELDS = ("n_src", "n_dst", "pairs", "reachable", "violations", "bad_sources")
+
+    def _intent_sets(self, src, dst, K: int) -> Tuple[np.ndarray, np.ndarray, int]:
+        W = self.info()["W"]
+        sets = []
+        for a in (src, dst):
+            a = np.ascontiguousarray(a, dtype=np.uint64)
+            if a.size != K * W:
+                raise ValueError(f"{K} sets of {W} words expected, got {a.size} words")
+            sets.append(a.reshape(K, W))
+        return sets[0], sets[1], W
+
+    def intents(self, src, dst, flags) -> dict:
+        """K intents at once: ``src`` / ``dst`` are (K, W) u64 bit sets over
+        the pods, ``flags`` K int32 (INTENT_ALLOW: an allow intent, else deny;
+        INTENT_SELF: the pairs (i, i) count).  Returns ``out`` (int64 (K, 6):
+        INTENT_FIELDS, over the sources among the rows this context holds)
+        and ``witness`` (int32 (K, 2): the smallest violating (i, j), or
+        (-1, -1)).  A call of more than INTENT_MAX_WORDS set words a side goes
+        to the library in slices of K."""
+        flags = np.ascontiguousarray(flags, dtype=np.int32).reshape(-1)
+        K = int(flags.shape[0])
+        src, dst, W = self._intent_sets(src, dst, K)
+        out = np.zeros((K, 6), dtype=np.int64)
+        wit = np.full((K, 2), -1, dtype=np.int32)
+        step = max(1, self.INTENT_MAX_WORDS // max(W, 1))
+        for k0 in range(0, K, step):
+            k1 = min(K, k0 + step)
+            self._chk(self.lib.kano_intents(self.ctx, k1 - k0, _ptr(src[k0:k1]), _ptr(dst[k0:k1]),
+                                            _ptr(flags[k0:k1]), _ptr(out[k0:k1]),
+                                            _ptr(wit[k0:k1])), "kano_intents")
+        return dict(out=out, witness=wit)
+
+    def intent_count(self, src, dst, flags: int) -> int:
+        """The number of pairs ``intent_pairs`` would return."""
+        src, dst, _ = self._intent_sets(src, dst, 1)
+        cnt = c_int64(0)
+        self._chk(self.lib.kano_intent_pairs(self.ctx, _ptr(src), _ptr(dst), int(flags), 0,
+                                             byref(cnt), None), "kano_intent_pairs")
+        return int(cnt.value)
+
+    def intent_pairs(self, src, dst, flags: int, limit: int = 1_000_000) -> np.ndarray:
+        """One intent's violating (i, j) pairs among the held rows, int32
+        (T, 2), ascending by i then j.  More than ``limit`` pairs raise
+        OverflowError."""
+        count = self.intent_count(src, dst, flags)
+        if count > int(limit):
+            raise OverflowError(f"{count} pairs exceed the limit of {int(limit)}")
+        out = np.empty((count, 2), dtype=np.int32)
+        if count:
+            src, dst, _ = self._intent_sets(src, dst, 1)
+            cnt = c_int64(0)
+            self._chk(self.lib.kano_intent_pairs(self.ctx, _ptr(src), _ptr(dst), int(flags), count,
+                                                 byref(cnt), _ptr(out)), "kano_intent_pairs")
+        return out
+
+    def intents_time(self) -> float:
+        """The last intents' device time (ms; KANO_TUNE=timing=1)."""
+        ms = ctypes.c_float(0.0)
+        self._chk(self.lib.kano_intents_time(self.ctx, byref(ms)), "kano_intents_time")
+        return float(ms.value)
+
     def rows_timing(self, reset: bool = False) -> dict:
         """k_rows launch times (HIP events) since the last reset: sum, count,
         min, max (ms); waits for the context's work."""

@@ -77,6 +77,11 @@ SIGNATURES = {
                                POINTER(c_int64)]),
     "kano_hop_pairs_fetch": (c_int, [c_void_p, c_void_p]),
     "kano_hops_time": (c_int, [c_void_p, POINTER(c_float)]),
+    "kano_intents": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_void_p]),
+    "kano_intent_pairs": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int64,
+                                  POINTER(c_int64), c_void_p]),
+    "kano_intents_time": (c_int, [c_void_p, POINTER(c_float)]),
     "kano_verify": (c_int, [c_void_p, c_int, c_void_p, c_int32, c_int64, c_void_p, c_void_p,
                             c_void_p, c_int64, POINTER(c_int64)]),
     "kano_verify_shard": (c_int, [c_void_p, c_int, c_void_p, c_int32, c_int64, c_int, c_void_p]),

@@ -706,3 +706,75 @@ def path_witness(matrix: ReachabilityMatrix, i: int, j: int, max_hops: int = 0) 
     """The canonical shortest path from i to j as a list of pod indices
     ([] when j is unreachable from i, or not within max_hops)."""
     return path_witnesses(matrix, [(int(i), int(j))], max_hops).of(0)
+
+
+# ---------------------------------------------------------------------------
+# What the cluster is supposed to do.  Not part of kano_py's algorithm.py.
+# The checks above are fixed questions; an Intent (kano/intent.py) is the
+# operator's own: "no src pod may reach a dst pod" (deny) or "every src pod
+# must reach every dst pod" (allow), src and dst being selectors over the
+# pods' labels, index sets or bit sets, free to overlap.  With S the src pods
+# among the held rows, D the dst pods and the considered pairs
+#   C = {(i, j) : i in S, j in D, and i != j unless self_pairs},
+# a deny intent's violations are the pairs of C with M[i, j] = 1, an allow
+# intent's those with M[i, j] = 0.  All intents of a call are checked in one
+# pass on the device from the matrix itself (kano_intents), so it holds for
+# built, updated, edited, loaded, snapshot, path and edge matrices alike.  A
+# matrix holding a row shard answers for the sources among its rows.  A
+# violating pair goes to why_reachable / path_witness, a violated intent's
+# pairs (intent_violations) to policy_blame.
+
+from .intent import Intent, Selector, load_intents, resolve_selectors  # noqa: E402,F401
+
+
+class IntentReport(NamedTuple):
+    n_src: np.ndarray          # int64, one entry per intent: src pods among the held rows
+    n_dst: np.ndarray          # int64: dst pods
+    pairs: np.ndarray          # int64: pairs considered
+    reachable: np.ndarray      # int64: considered pairs with M[i, j] = 1
+    violations: np.ndarray     # int64: deny: reachable; allow: pairs - reachable
+    bad_sources: np.ndarray    # int64: src pods with at least one violating pair
+    witness: np.ndarray        # int32 (K, 2): the smallest violating (i, j), or (-1, -1)
+    ok: np.ndarray             # bool: violations == 0
+
+    def failed(self) -> np.ndarray:
+        """The indices of the violated intents, ascending."""
+        return np.flatnonzero(~np.asarray(self.ok, dtype=bool))
+
+
+def _intent_flags(eng, kind: str, self_pairs: bool) -> int:
+    if kind not in ("deny", "allow"):
+        raise ValueError(f"kind must be 'deny' or 'allow', not {kind!r}")
+    return (eng.INTENT_ALLOW if kind == "allow" else 0) | (eng.INTENT_SELF if self_pairs else 0)
+
+
+def check_intents(matrix: ReachabilityMatrix, containers: List[Container], intents,
+                  self_pairs: bool = False) -> IntentReport:
+    """Every intent of ``intents`` (Intent tuples, or (src, dst, kind)
+    triples) against the matrix, in input order (see IntentReport)."""
+    eng, n, _ = _group_engine(matrix, containers)
+    intents = [Intent(*it) for it in intents]
+    K = len(intents)
+    flags = np.array([_intent_flags(eng, it.kind, self_pairs) for it in intents], dtype=np.int32)
+    sets = resolve_selectors(containers, [it.src for it in intents] + [it.dst for it in intents])
+    if n == 0 or K == 0:
+        z = np.zeros(K, np.int64)
+        return IntentReport(z, z.copy(), z.copy(), z.copy(), z.copy(), z.copy(),
+                            np.full((K, 2), -1, np.int32), np.ones(K, bool))
+    r = eng.intents(sets[:K], sets[K:], flags)
+    o = r["out"]
+    return IntentReport(*(o[:, f].copy() for f in range(6)), r["witness"], o[:, 4] == 0)
+
+
+def intent_violations(matrix: ReachabilityMatrix, containers: List[Container], intent,
+                      limit: int = 1_000_000, self_pairs: bool = False) -> np.ndarray:
+    """One intent's violating (i, j) pairs as an int32 (T, 2) array, ascending
+    by i then j (a row shard: the sources among its rows).  More than
+    ``limit`` pairs raise OverflowError naming their number."""
+    eng, n, _ = _group_engine(matrix, containers)
+    it = Intent(*intent)
+    flags = _intent_flags(eng, it.kind, self_pairs)
+    if n == 0:
+        return np.zeros((0, 2), np.int32)
+    sets = resolve_selectors(containers, [it.src, it.dst])
+    return eng.intent_pairs(sets[0], sets[1], flags, limit=limit)

@@ -555,6 +555,40 @@ class MultiBuild:
     def hops_time(self) -> float:
         return self._hops_member().hops_time()
 
+    # -- check_intents --------------------------------------------------------------
+    INTENT_ALLOW, INTENT_SELF = DeviceBuild.INTENT_ALLOW, DeviceBuild.INTENT_SELF
+
+    def intents(self, src, dst, flags) -> dict:
+        """DeviceBuild.intents over the row-sharded matrix: the members' counts
+        summed (n_dst, the same on every member with rows, taken once), the
+        smallest of their witnesses."""
+        parts = [m.intents(src, dst, flags) for m in self.members]
+        out = np.sum([p["out"] for p in parts], axis=0, dtype=np.int64)
+        out[:, 1] = np.max([p["out"][:, 1] for p in parts], axis=0)
+        # (i, j) packed so that (-1, -1) sorts last
+        keys = []
+        for p in parts:
+            w = p["witness"].astype(np.uint32).astype(np.uint64)
+            keys.append((w[:, 0] << np.uint64(32)) | w[:, 1])
+        key = np.min(keys, axis=0)
+        wit = np.stack([key >> np.uint64(32), key & np.uint64(0xffffffff)], axis=1)
+        return dict(out=out, witness=wit.astype(np.uint32).astype(np.int32))
+
+    def intent_count(self, src, dst, flags: int) -> int:
+        return sum(m.intent_count(src, dst, flags) for m in self.members)
+
+    def intent_pairs(self, src, dst, flags: int, limit: int = 1_000_000) -> np.ndarray:
+        """The members' pairs in rank order (= row order)."""
+        count = self.intent_count(src, dst, flags)
+        if count > int(limit):
+            raise OverflowError(f"{count} pairs exceed the limit of {int(limit)}")
+        parts = [m.intent_pairs(src, dst, flags, limit=count) for m in self.members]
+        return np.concatenate(parts).reshape(-1, 2)
+
+    def intents_time(self) -> float:
+        """The members' last intents' device times, summed."""
+        return sum(m.intents_time() for m in self.members)
+
     # -- measurement ------------------------------------------------------------
     def exchange_timing(self, enable: Optional[bool] = None, reset: bool = False) -> dict:
         """The verify exchange's time on member 0's stream (HIP events around
