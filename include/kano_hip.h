@@ -271,6 +271,53 @@ int kano_pair_policies_lists(kano_ctx* ctx, int64_t n_lists, int64_t nbits, int6
  * the offsets' scan and the emit pass; no copies). */
 int kano_pair_policies_time(kano_ctx* ctx, float* ms);
 
+/* port_matrix / pair_ports: port-aware reachability.  Both read the tables
+ * kano_pair_policies reads, over the same policies (the build's that are not
+ * removed plus the added ones that are not removed), and index them by engine
+ * id: 0 .. P-1 the build's, then the added ones; nids = P + added, and the
+ * entries of removed ids are ignored.  The engine knows no ports: the caller
+ * says which policies to keep (keep) or which bits each policy carries
+ * (pmask); kano/ports.py builds both from Policy.protocol.
+ * kano_policy_subset: dst's rows := the matrix of the kept policies,
+ *   subset[i,j] = 1 iff some alive p with keep[p] != 0 has i in select_p and
+ *   j in allow_p,
+ * for the rows r0..r1 both contexts hold.  dst is a matrix context of the same
+ * n, device and rows as src (kano_set_shard with the same range on an empty
+ * build); every word of every held row of dst is written (a pod no kept
+ * policy selects gets a zero row, bits at positions >= n are zero) and dst
+ * then reads as an edited matrix, like kano_path's destination.  The rows of
+ * row shards concatenate.  info (nullable) = [kept alive build policies, kept
+ * alive added policies, row classes of src with at least one kept policy].
+ * kano_pair_masks: out[q*KW + w] = OR of pmask[p*KW + w] over pols(i,j) of
+ * pair q (kano_pair_policies' pols), 0 iff cover(i,j) = 0; pairs in any
+ * order, duplicates allowed.  On a row shard a pair whose i lies outside
+ * r0..r1 gets a zero mask, so the masks of row shards OR together.
+ * -EINVAL: a NULL argument (pairs and out may be NULL with Q == 0, info
+ * always), src == dst, contexts of different n, device or rows, nids != P +
+ * added, KW <= 0, Q < 0, a context holding policy lists, a context whose
+ * matrix has no policies (as kano_pair_policies); -ERANGE: a pair index
+ * outside [0, n); -ENOTSUP: kano_policy_subset over more than 1,048,560 row
+ * classes; -ENOMEM (with a message): a device buffer could not be allocated.
+ * kano_policy_subset reports its errors on dst.  Q == 0, n == 0
+ * or no held rows give empty or zero results and launch nothing.  Exact bits.
+ * The device buffers are the call's own (the flags, the class-level rows
+ * U * ldC words and their bit-transposed 16-row groups; the pairs, the masks
+ * and the result), freed on return: src's matrix (never read), its class
+ * tables and every stored check result (column words, crosscheck words,
+ * shadow, conflict and pair_policies lists, impact) are unchanged, a call
+ * between pipelined kano_verify steps leaves the next step's results
+ * unchanged, and the context stays usable after every error. */
+int kano_policy_subset(kano_ctx* src, kano_ctx* dst, int64_t nids,
+                       const uint8_t* keep /* nids */,
+                       int64_t* info /* 3, nullable */);
+int kano_pair_masks(kano_ctx* ctx, int64_t Q, const int32_t* pairs /* 2*Q */,
+                    int64_t nids, int32_t KW, const uint64_t* pmask /* nids*KW */,
+                    uint64_t* out /* Q*KW */);
+/* KANO_TUNE timing=1: the last call's device time in ms (the fills and the
+ * kernels, no copies; kano_policy_subset's on src and on dst alike), else 0. */
+int kano_policy_subset_time(kano_ctx* ctx, float* ms);
+int kano_pair_masks_time(kano_ctx* ctx, float* ms);
+
 /* matrix_diff: what a change adds and removes.  a and b hold matrices of the
  * same n on the same device over the same rows r0..r1 (built, loaded, path or
  * edge matrices alike); for i in [r0, r1), j in [0, n):

@@ -171,6 +171,8 @@ struct kano_ctx {
   int impact_form = 0;       // impf=1/2: policy_impact's list / row form forced (0: by density)
   int pair_form = 0;         // ppf=1/2: pair_policies' lane / wave form forced (0: by list length)
   int pair_grid = 0;         // ppgrid=K: at most K blocks for k_pair_lane / k_pair_wave (0: 8 per CU)
+  int pmask_form = 0;        // pmf=1/2: kano_pair_masks' lane / wave form forced (0: as pair_policies')
+  int pmask_grid = 0;        // pmgrid=K: at most K blocks for k_pmask_lane / k_pmask_wave (0: 8 per CU)
   int diff_grid = 0;         // dgrid=K: at most K blocks for k_diff_rows (0: every resident block)
   int group_grid = 0;        // ggrid=K: at most K blocks for k_group_rows (0: every resident block)
   int group_batches = 0;     // gbatch=K: at most K batches of 64 destination groups in one
@@ -302,6 +304,11 @@ struct kano_ctx {
   // check_intents (kano_intents / kano_intent_pairs): the device buffers are
   // the call's own; only the time stays
   float intents_ms = 0.f;     // timing=1: the last kano_intents' kernels (kano_intents_time)
+  // port_matrix / pair_ports (kano_policy_subset / kano_pair_masks): the
+  // device buffers are the call's own; only the times stay (kano_policy_subset
+  // leaves its time on the source and on the destination)
+  float subset_ms = 0.f;      // timing=1: the last kano_policy_subset's fills + kernels
+  float pmask_ms = 0.f;       // timing=1: the last kano_pair_masks' kernel
   // policy_shadow count-only (kano_verify with shadow_cap < 0): the grouped
   // count (k_shg_*) instead of the pair-by-pair flags
   bool vs_count_only = false;

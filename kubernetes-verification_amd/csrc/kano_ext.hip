@@ -10,6 +10,7 @@
 #include "kano_path.hpp"
 #include "kano_hops.hpp"
 #include "kano_intents.hpp"
+#include "kano_ports.hpp"
 
 using namespace kano_eng;
 
@@ -69,6 +70,46 @@ int path_t_local(kano_ctx* src, kano_ctx* ctx, u64* Tout) {
                        base, ldR, P_<int32_t>(src->rc.cls), P_<int32_t>(src->cc.moff),
                        P_<int32_t>(src->cc.mem), Ua, KW, nch, src->r0, src->r1, Tout);
   }
+  KLAUNCH();
+  return 0;
+}
+
+// ctx's pod rows from class-level rows over src's classes (kano_path's last
+// step, kano_policy_subset's write): M[i] bit j = R[rc(i)][cc(j)] for every
+// row i that ctx and src hold.  R (rows x ldR words, Ua column classes) is
+// bit-transposed into 16-row groups (rt16: ceil(rows / 16) * Ua uint16, the
+// caller's), then one block per (group, word range) expands a chunk of the
+// class rows and streams it to the member rows (k_path_expand16).  Every word
+// of every held row is written, the bits at positions >= n as zeros.
+int path_expand_rows(kano_ctx* ctx, kano_ctx* src, const u64* R, i64 ldR, i64 rows, i64 Ua,
+                     void* rt16v) {
+  const i64 n = src->n, ldM = ctx->ldM;
+  const i64 ng = (rows + 15) / 16, RW = (rows + 63) / 64, CWn = (Ua + 63) / 64;
+  const i64 CG = (CWn + 15) / 16;
+  hipLaunchKernelGGL(k_bit_transpose<true>, dim3(nblk(RW * CG, TPB / 64)), dim3(TPB), 0,
+                     ctx->stream, R, ldR, rows, RW, CG, Ua, rt16v, Ua, ng);
+  KLAUNCH();
+  constexpr int SUB = 2;
+  // member slices when the (group, word range) blocks alone cannot fill
+  // the chip and the classes are large (broad selectors)
+  const i64 gxy = (i64)nblk(ldM, (i64)TPB * SUB) * ng;
+  const i64 avg_members = (n + rows - 1) / rows;
+  const i64 Z = std::max<i64>(1, std::min<i64>({(2048 + gxy - 1) / gxy, avg_members / 8, 64}));
+  const dim3 grid(nblk(ldM, (i64)TPB * SUB), (unsigned)ng, (unsigned)Z);
+  const size_t lds = sizeof(uint16_t) * (size_t)Ua;
+  const uint16_t* rt16 = reinterpret_cast<const uint16_t*>(rt16v);
+  const bool use_lds = lds <= 64 * 1024 && ctx->path_lds;
+  const bool staged = avg_members >= 16;
+  auto launch = [&](auto kern, size_t shm) {   // (by handle: see launch_marked)
+    hipExtLaunchKernelGGL(kern, grid, dim3(TPB), (std::uint32_t)shm, ctx->stream, nullptr,
+                          nullptr, 0, rt16, Ua, rows,
+                       P_<int32_t>(src->cc.cls), n, P_<int32_t>(src->rc.moff),
+                       P_<int32_t>(src->rc.mem), P_<u64>(ctx->M), ldM, src->r0);
+  };
+  if (use_lds && staged) launch(k_path_expand16<SUB, true, true>, lds);
+  else if (use_lds) launch(k_path_expand16<SUB, true, false>, lds);
+  else if (staged) launch(k_path_expand16<SUB, false, true>, 0);
+  else launch(k_path_expand16<SUB, false, false>, 0);
   KLAUNCH();
   return 0;
 }
@@ -203,36 +244,8 @@ int path_impl(kano_ctx* src, kano_ctx* ctx, int hops, int mode, int64_t* info, b
         KCHK(hipMemcpyAsync(Rb[0], Rb[ri], sizeof(u64) * Rw, hipMemcpyDeviceToDevice,
                             ctx->stream));
     } else {
-      // P[i] bit j = R[rc(i)][cc(j)]: R bit-transposed into 16-row groups,
-      // then one block per (group, word range)
-      const i64 ng = (g.rows + 15) / 16, RW = (g.rows + 63) / 64, CWn = (g.Ua + 63) / 64;
-      KTRY(dalloc(ctx, ctx->pA, sizeof(uint16_t) * ng * g.Ua));
-      const i64 CG = (CWn + 15) / 16;
-      hipLaunchKernelGGL(k_bit_transpose<true>, dim3(nblk(RW * CG, TPB / 64)), dim3(TPB), 0,
-                         ctx->stream, Rb[ri], g.ldR, g.rows, RW, CG, g.Ua, ctx->pA.p, g.Ua, ng);
-      KLAUNCH();
-      constexpr int SUB = 2;
-      // member slices when the (group, word range) blocks alone cannot fill
-      // the chip and the classes are large (broad selectors)
-      const i64 gxy = (i64)nblk(ldM, (i64)TPB * SUB) * ng;
-      const i64 avg_members = (n + g.rows - 1) / g.rows;
-      const i64 Z = std::max<i64>(1, std::min<i64>({(2048 + gxy - 1) / gxy, avg_members / 8, 64}));
-      const dim3 grid(nblk(ldM, (i64)TPB * SUB), (unsigned)ng, (unsigned)Z);
-      const size_t lds = sizeof(uint16_t) * (size_t)g.Ua;
-      const uint16_t* rt16 = reinterpret_cast<const uint16_t*>(ctx->pA.p);
-      const bool use_lds = lds <= 64 * 1024 && ctx->path_lds;
-      const bool staged = avg_members >= 16;
-      auto launch = [&](auto kern, size_t shm) {   // (by handle: see launch_marked)
-        hipExtLaunchKernelGGL(kern, grid, dim3(TPB), (std::uint32_t)shm, ctx->stream, nullptr,
-                              nullptr, 0, rt16, g.Ua, g.rows,
-                           P_<int32_t>(src->cc.cls), n, P_<int32_t>(src->rc.moff),
-                           P_<int32_t>(src->rc.mem), P_<u64>(ctx->M), ldM, src->r0);
-      };
-      if (use_lds && staged) launch(k_path_expand16<SUB, true, true>, lds);
-      else if (use_lds) launch(k_path_expand16<SUB, true, false>, lds);
-      else if (staged) launch(k_path_expand16<SUB, false, true>, 0);
-      else launch(k_path_expand16<SUB, false, false>, 0);
-      KLAUNCH();
+      KTRY(dalloc(ctx, ctx->pA, sizeof(uint16_t) * ((g.rows + 15) / 16) * g.Ua));
+      KTRY(path_expand_rows(ctx, src, Rb[ri], g.ldR, g.rows, g.Ua, ctx->pA.p));
     }
   } else if (n > 0 && W > 0) {
     // one hop (or an empty class set): the matrix itself
@@ -1665,6 +1678,239 @@ int kano_intent_pairs(kano_ctx* ctx, const uint64_t* src, const uint64_t* dst, i
 int kano_intents_time(kano_ctx* ctx, float* ms) {
   if (!ctx || !ms) return -EINVAL;
   *ms = ctx->intents_ms;
+  return 0;
+}
+
+}  // extern "C"
+
+// ===========================================================================
+// port_matrix / pair_ports: a subset of the policies' matrix and the pairs'
+// port masks from the resident tables (k_ports_*, k_pmask_*, kano_ports.hpp;
+// the class rows' expansion is kano_path's, path_expand_rows).  The matrix of
+// the source is not read and nothing of the source is written.
+// ===========================================================================
+namespace {
+
+const char* const NO_POLICIES =
+    ": the matrix has no policies (an empty, copied, loaded, path or edge matrix holds rows only)";
+
+}  // namespace
+
+extern "C" {
+
+int kano_policy_subset(kano_ctx* src, kano_ctx* dst, int64_t nids, const uint8_t* keep,
+                       int64_t* info) {
+  if (!src || !dst) return -EINVAL;
+  if (src == dst)
+    return fail(dst, -EINVAL, "kano_policy_subset: the destination must be another context");
+  if (src->device != dst->device)
+    return fail(dst, -EINVAL, "kano_policy_subset: contexts on two devices");
+  kano_ctx* ctx = dst;
+  KCHK(hipSetDevice(dst->device));
+  {
+    const int rc = ensure_built(src);
+    if (rc) return fail(dst, rc, "kano_policy_subset: source: " + src->err);
+  }
+  if (src->lists_mode)
+    return fail(dst, -EINVAL, "kano_policy_subset: the source holds policy lists, not a matrix");
+  const i64 P = src->P, A = src->inc_A;
+  if (P == 0 && A == 0) return fail(dst, -EINVAL, std::string("kano_policy_subset") + NO_POLICIES);
+  if (nids != P + A)
+    return fail(dst, -EINVAL, "kano_policy_subset: nids = " + std::to_string(nids) + ", the source has " +
+                                  std::to_string(P + A) + " engine ids");
+  if (!keep) return fail(dst, -EINVAL, "kano_policy_subset: keep is NULL");
+  KTRY(ensure_matrix(dst));
+  if (dst->n != src->n || dst->r0 != src->r0 || dst->r1 != src->r1 || dst->ldM != src->ldM)
+    return fail(dst, -EINVAL, "kano_policy_subset: the destination must hold the same rows of a "
+                              "matrix of the same size");
+  {
+    const int rc = sync(src);   // the source's classes are complete
+    if (rc) return fail(dst, rc, "kano_policy_subset: source: " + src->err);
+  }
+  // use[p]: alive and kept
+  std::vector<uint8_t> use((size_t)nids);
+  i64 kept_build = 0, kept_added = 0;
+  for (i64 p = 0; p < nids; ++p) {
+    use[p] = keep[p] && !src->dead[p];
+    (p < P ? kept_build : kept_added) += use[p];
+  }
+  const i64 n = dst->n, W = dst->W, ldM = dst->ldM, r0 = dst->r0, rl = rows_local(dst);
+  const i64 U = src->rc.U, Ua = src->cc.U, ldC = src->ldC;
+  const bool classes = P > 0 && U > 0 && Ua > 0;
+  if (classes && (U + 15) / 16 > 65535)
+    return fail(dst, -ENOTSUP, "kano_policy_subset: more than 1,048,560 row classes");
+  src->subset_ms = dst->subset_ms = 0.f;
+  unsigned kept_classes = 0;
+  DBuf used, mcs, rt16, cnt;
+  auto run = [&]() -> int {
+    KTRY(dalloc(ctx, used, (size_t)nids));
+    KTRY(dalloc(ctx, cnt, sizeof(unsigned)));
+    KCHK(hipMemcpyAsync(used.p, use.data(), (size_t)nids, hipMemcpyHostToDevice, ctx->stream));
+    if (classes) {
+      KTRY(dalloc(ctx, mcs, sizeof(u64) * (size_t)(U * ldC)));
+      KTRY(dalloc(ctx, rt16, sizeof(uint16_t) * (size_t)(((U + 15) / 16) * Ua)));
+    }
+    hipEvent_t tev[2] = {nullptr, nullptr};
+    if (src->stage_timing || dst->stage_timing) {
+      KCHK(hipEventCreate(&tev[0]));
+      KCHK(hipEventCreate(&tev[1]));
+      KCHK(hipEventRecord(tev[0], ctx->stream));
+    }
+    KCHK(hipMemsetAsync(cnt.p, 0, sizeof(unsigned), ctx->stream));
+    const uint8_t* use_d = P_<uint8_t>(used);
+    if (classes) {
+      int wl = 1;
+      while (wl < TPB && wl < ldC) wl <<= 1;
+      const i64 cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
+      hipLaunchKernelGGL(k_ports_class, dim3((unsigned)std::min<i64>(U, cus * 8)), dim3(TPB), 0,
+                         ctx->stream, U, (const i64*)P_<i64>(src->soffc),
+                         (const int32_t*)P_<int32_t>(src->slist), use_d,
+                         (const u64*)P_<u64>(src->AC), ldC, wl, P_<u64>(mcs), P_<unsigned>(cnt));
+      KLAUNCH();
+      // the class rows to the member rows: every word of every held row
+      KTRY(path_expand_rows(ctx, src, P_<u64>(mcs), ldC, U, Ua, rt16.p));
+    }
+    // the added policies OR-ed in; without classes the rows start as zeros
+    if (!classes || kept_added > 0) {
+      hipLaunchKernelGGL(k_ports_rows, dim3(nblk(rl * (ldM / 2))), dim3(TPB), 0, ctx->stream,
+                         classes ? 1 : 0, use_d, P, (const u64*)P_<u64>(src->asel),
+                         (const u64*)P_<u64>(src->aalw), W, kept_added > 0 ? A : 0, r0, rl, ldM,
+                         P_<u64>(dst->M));
+      KLAUNCH();
+    }
+    if (tev[0]) {
+      KCHK(hipEventRecord(tev[1], ctx->stream));
+      KCHK(hipEventSynchronize(tev[1]));
+      float ms = 0.f;
+      (void)hipEventElapsedTime(&ms, tev[0], tev[1]);
+      src->subset_ms = dst->subset_ms = ms;
+      (void)hipEventDestroy(tev[0]);
+      (void)hipEventDestroy(tev[1]);
+    }
+    KCHK(hipMemcpyAsync(&kept_classes, cnt.p, sizeof(unsigned), hipMemcpyDeviceToHost,
+                        ctx->stream));
+    return sync(ctx);
+  };
+  int rc = 0;
+  if (n > 0 && rl > 0) {
+    rc = run();
+    if (rc) (void)hipStreamSynchronize(ctx->stream);   // nothing in flight on the temporaries
+    for (DBuf* b : {&used, &mcs, &rt16, &cnt}) dfree(*b);
+    dst->cols_valid = false;
+    dst->rows_dirty = true;
+    dst->user_edited = true;
+  }
+  if (rc) return rc;
+  if (info) {
+    info[0] = kept_build;
+    info[1] = kept_added;
+    info[2] = (int64_t)kept_classes;
+  }
+  return 0;
+}
+
+int kano_pair_masks(kano_ctx* ctx, int64_t Q, const int32_t* pairs, int64_t nids, int32_t KW,
+                    const uint64_t* pmask, uint64_t* out) {
+  KTRY(ensure_built(ctx));
+  if (ctx->lists_mode)
+    return fail(ctx, -EINVAL, "kano_pair_masks: the context holds policy lists, not a matrix");
+  const i64 P = ctx->P, A = ctx->inc_A;
+  if (P == 0 && A == 0) return fail(ctx, -EINVAL, std::string("kano_pair_masks") + NO_POLICIES);
+  if (Q < 0 || KW <= 0) return fail(ctx, -EINVAL, "kano_pair_masks: Q < 0 or KW <= 0");
+  if (nids != P + A)
+    return fail(ctx, -EINVAL, "kano_pair_masks: nids = " + std::to_string(nids) + ", the context has " +
+                                  std::to_string(P + A) + " engine ids");
+  if (!pmask || (Q > 0 && (!pairs || !out)))
+    return fail(ctx, -EINVAL, "kano_pair_masks: pairs, pmask or out is NULL");
+  const i64 n = ctx->n;
+  for (i64 q = 0; q < Q; ++q)
+    if (pairs[2 * q] < 0 || pairs[2 * q] >= n || pairs[2 * q + 1] < 0 || pairs[2 * q + 1] >= n)
+      return fail(ctx, -ERANGE, "kano_pair_masks: pair " + std::to_string(q) + " out of range");
+  ctx->pmask_ms = 0.f;
+  if (Q == 0) return 0;
+  const size_t b_out = sizeof(u64) * (size_t)Q * (size_t)KW;
+  if (rows_local(ctx) <= 0) {
+    std::memset(out, 0, b_out);
+    return 0;
+  }
+  const bool any_dead = std::find(ctx->dead.begin(), ctx->dead.end(), 1) != ctx->dead.end();
+  DBuf pr, pm, dd, od;
+  auto run = [&]() -> int {
+    const size_t b_pm = sizeof(u64) * (size_t)nids * (size_t)KW;
+    KTRY(dalloc(ctx, pr, sizeof(int32_t) * 2 * (size_t)Q));
+    KTRY(dalloc(ctx, pm, b_pm));
+    KTRY(dalloc(ctx, od, b_out));
+    if (any_dead) KTRY(dalloc(ctx, dd, (size_t)nids));
+    KCHK(hipMemcpyAsync(pr.p, pairs, sizeof(int32_t) * 2 * (size_t)Q, hipMemcpyHostToDevice,
+                        ctx->stream));
+    KCHK(hipMemcpyAsync(pm.p, pmask, b_pm, hipMemcpyHostToDevice, ctx->stream));
+    if (any_dead)
+      KCHK(hipMemcpyAsync(dd.p, ctx->dead.data(), (size_t)nids, hipMemcpyHostToDevice,
+                          ctx->stream));
+    PairMaskArgs a{};
+    a.pairs = P_<int32_t>(pr);
+    a.Q = Q;
+    // (a build without policies has no classes: only the added part remains)
+    a.rcls = P > 0 && ctx->rc.U > 0 ? P_<int32_t>(ctx->rc.cls) : nullptr;
+    a.ccls = P_<int32_t>(ctx->cc.cls);
+    a.soffc = P_<i64>(ctx->soffc);
+    a.slist = P_<int32_t>(ctx->slist);
+    a.dead = any_dead ? P_<uint8_t>(dd) : nullptr;
+    a.AC = P_<u64>(ctx->AC);
+    a.ldC = ctx->ldC;
+    a.P = P;
+    a.asel = P_<u64>(ctx->asel);
+    a.aalw = P_<u64>(ctx->aalw);
+    a.W = ctx->W;
+    a.A = A;
+    a.r0 = ctx->r0;
+    a.r1 = ctx->r1;
+    a.pmask = P_<u64>(pm);
+    a.KW = KW;
+    a.out = P_<u64>(od);
+    if (a.rcls && !a.ccls) return fail(ctx, -EINVAL, "kano_pair_masks: no column classes");
+    // the form as kano_pair_policies picks it: by the mean list a pair walks
+    const i64 U = ctx->rc.U;
+    const i64 sbar = (a.rcls ? (ctx->nnz_sel + U - 1) / U : 0) + A;
+    bool wave = sbar > PMASK_WAVE_MIN;
+    if (ctx->pmask_form) wave = ctx->pmask_form == 2;
+    const i64 cap = ctx->pmask_grid > 0 ? ctx->pmask_grid : (i64)std::max(1, ctx->num_cus) * 8;
+    const unsigned grid =
+        (unsigned)std::min<i64>(cap, wave ? (Q + TPB / 64 - 1) / (TPB / 64) : nblk(Q));
+    hipEvent_t tev[2] = {nullptr, nullptr};
+    if (ctx->stage_timing) {
+      KCHK(hipEventCreate(&tev[0]));
+      KCHK(hipEventCreate(&tev[1]));
+      KCHK(hipEventRecord(tev[0], ctx->stream));
+    }
+    if (wave) hipLaunchKernelGGL(k_pmask_wave, dim3(grid), dim3(TPB), 0, ctx->stream, a);
+    else hipLaunchKernelGGL(k_pmask_lane, dim3(grid), dim3(TPB), 0, ctx->stream, a);
+    KLAUNCH();
+    if (tev[0]) {
+      KCHK(hipEventRecord(tev[1], ctx->stream));
+      KCHK(hipEventSynchronize(tev[1]));
+      (void)hipEventElapsedTime(&ctx->pmask_ms, tev[0], tev[1]);
+      (void)hipEventDestroy(tev[0]);
+      (void)hipEventDestroy(tev[1]);
+    }
+    KCHK(hipMemcpyAsync(out, od.p, b_out, hipMemcpyDeviceToHost, ctx->stream));
+    return sync(ctx);
+  };
+  const int rc = run();
+  if (rc) (void)hipStreamSynchronize(ctx->stream);   // nothing in flight on the temporaries
+  for (DBuf* b : {&pr, &pm, &dd, &od}) dfree(*b);
+  return rc;
+}
+
+int kano_policy_subset_time(kano_ctx* ctx, float* ms) {
+  if (!ctx || !ms) return -EINVAL;
+  *ms = ctx->subset_ms;
+  return 0;
+}
+
+int kano_pair_masks_time(kano_ctx* ctx, float* ms) {
+  if (!ctx || !ms) return -EINVAL;
+  *ms = ctx->pmask_ms;
   return 0;
 }
 

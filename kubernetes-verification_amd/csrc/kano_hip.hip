@@ -2346,6 +2346,8 @@ int kano_create(int device, kano_ctx** out) {
         if (k == "impf" && v >= 0 && v <= 2) ctx->impact_form = v;
         if (k == "ppf" && v >= 0 && v <= 2) ctx->pair_form = v;
         if (k == "ppgrid" && v >= 0) ctx->pair_grid = v;
+        if (k == "pmf" && v >= 0 && v <= 2) ctx->pmask_form = v;
+        if (k == "pmgrid" && v >= 0) ctx->pmask_grid = v;
         if (k == "dgrid" && v >= 0) ctx->diff_grid = v;
         if (k == "ggrid" && v >= 0) ctx->group_grid = v;
         if (k == "gbatch" && v >= 0) ctx->group_batches = v;

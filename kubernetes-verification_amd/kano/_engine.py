@@ -655,6 +655,52 @@ class DeviceBuild:
                   "kano_pair_policies_time")
         return float(ms.value)
 
+    # -- port_matrix / pair_ports (kano_policy_subset / kano_pair_masks) --
+    def nids(self) -> int:
+        """The engine ids in use: the build's and every added one, removed or
+        not (the length of subset_into's ``keep`` and pair_masks' ``pmask``)."""
+        return max(self.info()["P"], getattr(self, "_id_end", 0))
+
+    def subset_into(self, dst: "DeviceBuild", keep) -> dict:
+        """dst's rows := the matrix of the kept policies (kano_policy_subset):
+        ``keep`` holds one flag per engine id (the build's, then the added
+        ones; removed ids are ignored).  ``dst`` is a matrix context of the
+        same n, device and rows (DeviceBuild.empty(n, rows=...)); this
+        context's matrix and tables are not written."""
+        k = np.ascontiguousarray(np.asarray(keep).reshape(-1) != 0, dtype=np.uint8)
+        info = np.zeros(3, dtype=np.int64)
+        dst._chk(self.lib.kano_policy_subset(self.ctx, dst.ctx, int(k.shape[0]), _ptr(k),
+                                             _ptr(info)), "kano_policy_subset")
+        return dict(zip(("kept_build", "kept_added", "kept_classes"), map(int, info)))
+
+    def pair_masks(self, pairs, pmask) -> np.ndarray:
+        """The OR of ``pmask``'s rows ((engine ids, KW) uint64) over the
+        policies allowing each pod pair of ``pairs`` (kano_pair_masks): uint64
+        (Q, KW), zero where no policy does.  A row shard answers for the pairs
+        whose i it holds (the others get zeros)."""
+        pr, Q = _as_pairs(pairs)
+        pm = np.ascontiguousarray(pmask, dtype=np.uint64)
+        if pm.ndim != 2 or pm.shape[1] < 1:
+            raise ValueError("pmask must be an (engine ids, KW >= 1) array")
+        out = np.zeros((Q, pm.shape[1]), dtype=np.uint64)
+        self._chk(self.lib.kano_pair_masks(self.ctx, Q, _ptr(pr), int(pm.shape[0]),
+                                           int(pm.shape[1]), _ptr(pm), _ptr(out)),
+                  "kano_pair_masks")
+        return out
+
+    def subset_time(self) -> float:
+        """The last subset_into's device time (ms; KANO_TUNE=timing=1)."""
+        ms = ctypes.c_float(0.0)
+        self._chk(self.lib.kano_policy_subset_time(self.ctx, byref(ms)),
+                  "kano_policy_subset_time")
+        return float(ms.value)
+
+    def pair_masks_time(self) -> float:
+        """The last pair_masks' device time (ms; KANO_TUNE=timing=1)."""
+        ms = ctypes.c_float(0.0)
+        self._chk(self.lib.kano_pair_masks_time(self.ctx, byref(ms)), "kano_pair_masks_time")
+        return float(ms.value)
+
     # -- matrix_diff (kano_diff / kano_diff_pairs / kano_copy_matrix) -----
     DIFF_KINDS = {"added": 0, "removed": 1}
 

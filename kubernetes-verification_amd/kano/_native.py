@@ -64,6 +64,11 @@ SIGNATURES = {
                                          c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p,
                                          c_void_p, POINTER(c_int64)]),
     "kano_pair_policies_time": (c_int, [c_void_p, POINTER(c_float)]),
+    "kano_policy_subset": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "kano_pair_masks": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p,
+                                c_void_p]),
+    "kano_policy_subset_time": (c_int, [c_void_p, POINTER(c_float)]),
+    "kano_pair_masks_time": (c_int, [c_void_p, POINTER(c_float)]),
     "kano_diff": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "kano_diff_pairs": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64,
                                 POINTER(c_int64), c_void_p]),

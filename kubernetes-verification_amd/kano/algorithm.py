@@ -778,3 +778,146 @@ def intent_violations(matrix: ReachabilityMatrix, containers: List[Container], i
         return np.zeros((0, 2), np.int32)
     sets = resolve_selectors(containers, [it.src, it.dst])
     return eng.intent_pairs(sets[0], sets[1], flags, limit=limit)
+
+
+# ---------------------------------------------------------------------------
+# On which port.  Not part of kano_py's algorithm.py, whose maths ignore
+# Policy.protocol: M[i, j] = 1 only says "reachable on some port".  With the
+# port table of the matrix's current policies (kano/ports.py: slots 0 .. K-1
+# the named (protocol, port) keys, slot K = ANY_OTHER, a bit mask per policy)
+# and, as for pair_policies, the working sets of matrix._policies (current
+# indices; accumulated lists, quirk Q5, and bits edited by hand do not enter),
+#   subset(S)[i, j]  = 1 iff some p in S has i in select_p and j in allow_p
+#   port_matrix(k)   = subset({p : masks[p] has bit k})   (several ports: the
+#                      union of their slots)
+#   pair_ports(i, j) = OR of masks[p] over pols(i, j)   (0 iff cover(i, j) = 0)
+# computed on the device from the resident tables (kano_policy_subset /
+# kano_pair_masks) without touching the matrix, for built and incrementally
+# updated matrices alike.  A subset matrix is a rows-only ReachabilityMatrix
+# on the device (over a row shard: the same rows), so every check above,
+# matrix_diff, hop_*, group_reachability and check_intents read it.  Keys are
+# opaque: no port ranges, no named-port resolution.  kano.k8s (kubesv ignores
+# ports) and the parser stay as they are.
+
+from .ports import ANY_OTHER, PortSet, PortTable, key_slots, port_key, port_table  # noqa: E402,F401
+
+
+class PairPorts(NamedTuple):
+    keys: list                 # the table's (protocol, port) keys, slot order
+    masks: np.ndarray          # uint64 (Q, KW): bit k = open on slot k, bit K = ANY_OTHER
+
+    def of(self, q: int) -> list:
+        """The keys queried pair q is open on, in table order, ANY_OTHER last
+        when the pair is open on the ports no policy names."""
+        q = int(q)
+        if not -len(self.masks) <= q < len(self.masks):
+            raise IndexError("pair index out of range")
+        names = list(self.keys) + [ANY_OTHER]
+        return [names[k] for k in set_bit_indices(self.masks[q], len(names)).tolist()]
+
+    def on(self, port) -> np.ndarray:
+        """bool (Q,): the queried pairs open on the port (a (protocol, port)
+        key, ANY_OTHER, or a list of those: open on any of them)."""
+        m = np.zeros(self.masks.shape[1], dtype=np.uint64)
+        for s in key_slots(list(self.keys), port):
+            m[s >> 6] |= np.uint64(1) << np.uint64(s & 63)
+        return (self.masks & m).any(axis=1)
+
+
+def _engine_keep(eng, ids, indices, P: int) -> np.ndarray:
+    """keep flags over the engine ids for current policy indices."""
+    idx = np.asarray(list(indices), dtype=np.int64).reshape(-1)
+    if idx.size and (idx.min() < -P or idx.max() >= P):
+        raise IndexError("list index out of range")
+    idx = np.where(idx < 0, idx + P, idx)
+    keep = np.zeros(eng.nids(), dtype=np.uint8)
+    keep[idx if ids is None else ids[0][idx]] = 1
+    return keep
+
+
+def _empty_like(matrix: ReachabilityMatrix) -> ReachabilityMatrix:
+    """A rows-only matrix over the same pods, devices and rows, all zero."""
+    from ._engine import DeviceBuild
+    from .multi import MultiBuild
+    src = _engine(matrix, whole=False)
+    n = matrix.container_size
+    out = ReachabilityMatrix.__new__(ReachabilityMatrix)
+    out.container_size = n
+    out._engine = (MultiBuild.empty(n, src.G, devices=src.devices)
+                   if isinstance(src, MultiBuild)
+                   else DeviceBuild.empty(n, device=src.device, rows=src.row_span))
+    out._containers = None
+    out._policies = None
+    out._ncontainers = n
+    out._lists = None
+    return out
+
+
+def policy_subset_matrix(matrix: ReachabilityMatrix, indices) -> ReachabilityMatrix:
+    """The matrix of the policies ``indices`` alone (indices of the current
+    policy list; duplicates are fine, an index out of range raises
+    IndexError): what build_matrix over that sub-list gives, written on the
+    device from the resident tables into a new rows-only matrix."""
+    eng, _, ids, P = _pair_engine(matrix, [])
+    keep = _engine_keep(eng, ids, indices, P) if P else None
+    out = _empty_like(matrix)
+    if P and matrix.container_size:
+        try:
+            out.subset_info = eng.subset_into(out._engine, keep)
+        except BaseException:
+            out._engine.close()
+            raise
+    return out
+
+
+def _port_table(matrix: ReachabilityMatrix) -> PortTable:
+    return port_table(matrix._policies)
+
+
+def port_matrix(matrix: ReachabilityMatrix, port) -> ReachabilityMatrix:
+    """The pairs reachable on ``port``: a (protocol, port) key, ANY_OTHER, or
+    a list of those (reachable on any of them).  A key no policy names is
+    ANY_OTHER's slot: only the any-port policies open it."""
+    _pair_engine(matrix, [])
+    t = _port_table(matrix)
+    return policy_subset_matrix(matrix, np.flatnonzero(t.carries(t.slots(port))))
+
+
+def pair_ports(matrix: ReachabilityMatrix, pairs) -> PairPorts:
+    """For every (i, j) of ``pairs`` the ports the pair is open on (see
+    PairPorts); a matrix holding a row shard answers for the pairs whose i it
+    holds (the others get empty masks)."""
+    eng, pr, ids, P = _pair_engine(matrix, pairs)
+    t = _port_table(matrix)
+    if P == 0 or pr.shape[0] == 0:
+        return PairPorts(t.keys, np.zeros((pr.shape[0], t.KW), np.uint64))
+    pm = np.zeros((eng.nids(), t.KW), dtype=np.uint64)
+    pm[np.arange(P) if ids is None else ids[0]] = t.masks
+    return PairPorts(t.keys, eng.pair_masks(pr, pm))
+
+
+def reachable_on(matrix: ReachabilityMatrix, i: int, j: int, port) -> bool:
+    """Whether pod i reaches pod j on ``port`` (as port_matrix's argument)."""
+    return bool(pair_ports(matrix, [(int(i), int(j))]).on(port)[0])
+
+
+def port_exposure(matrix: ReachabilityMatrix) -> Tuple[list, np.ndarray]:
+    """(keys, int64 (K + 1,)): the pod pairs open on every slot of the port
+    table, ANY_OTHER's last, over the held rows (the counts of row shards add
+    up).  One subset matrix per slot into one reused destination, counted on
+    the device."""
+    eng, _, ids, P = _pair_engine(matrix, [])
+    t = _port_table(matrix)
+    n = matrix.container_size
+    counts = np.zeros(t.KS, dtype=np.int64)
+    if P == 0 or n == 0:
+        return t.keys, counts
+    out = _empty_like(matrix)
+    try:
+        z = np.zeros(n, dtype=np.int32)
+        for k in range(t.KS):
+            eng.subset_into(out._engine, _engine_keep(eng, ids, np.flatnonzero(t.carries([k])), P))
+            counts[k] = out._engine.group_counts(z, z, 1, 1)["counts"][0, 0]
+    finally:
+        out._engine.close()
+    return t.keys, counts

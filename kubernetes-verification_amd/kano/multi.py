@@ -348,6 +348,23 @@ class MultiBuild:
             out.update(offsets=off, policies=pol)
         return out
 
+    def nids(self) -> int:
+        return max(self.members[0].info()["P"], getattr(self, "_id_end", 0))
+
+    def subset_into(self, dst: "MultiBuild", keep) -> dict:
+        """DeviceBuild.subset_into member by member: every member writes its
+        own rows of dst (a group over the same devices and row shards)."""
+        self._same_shards(dst, "subset_into")
+        parts = [m.subset_into(d, keep) for m, d in zip(self.members, dst.members)]
+        out = dict(parts[0])
+        out["kept_classes"] = sum(p["kept_classes"] for p in parts)
+        return out
+
+    def pair_masks(self, pairs, pmask) -> np.ndarray:
+        """DeviceBuild.pair_masks over all rows: the members' masks OR-ed (a
+        pair is answered by the member holding its i, the others give 0)."""
+        return np.bitwise_or.reduce([m.pair_masks(pairs, pmask) for m in self.members])
+
     # -- matrix access: owners --------------------------------------------
     def rows(self, r0: int, nrows: int, out: Optional[np.ndarray] = None) -> np.ndarray:
         if out is None:
