@@ -318,6 +318,70 @@ int kano_pair_masks(kano_ctx* ctx, int64_t Q, const int32_t* pairs /* 2*Q */,
 int kano_policy_subset_time(kano_ctx* ctx, float* ms);
 int kano_pair_masks_time(kano_ctx* ctx, float* ms);
 
+/* verdict_matrix / pair_verdicts: deny rules and priorities (the tiers of
+ * AdminNetworkPolicy, Calico and Cilium policy sets).  Both read the tables
+ * kano_pair_policies reads, over the same policies and the same engine ids as
+ * kano_policy_subset (nids = P + added; the entries of removed ids are
+ * ignored).  Every policy p carries action[p] (0 allow, 1 deny) and an integer
+ * prio[p]: a smaller number is evaluated first, any int32 value is valid, and
+ * the C side ranks the raw values.  p matches (i, j) iff i in select_p and j
+ * in allow_p (source -> destination, the direction swap already applied).
+ *   t*(i,j)  = the smallest prio[p] over the matching policies
+ *   verdict  = none  if nothing matches (unreachable: kano's reading),
+ *              deny  if some deny policy with prio == t* matches (within one
+ *                    priority deny wins),
+ *              allow otherwise
+ *   decider  = the smallest engine id among the matching policies with
+ *              prio == t* and the winning action.
+ * All-allow with any priorities gives the built matrix; one priority for all
+ * gives subset(allows) & ~subset(denies).  Pass, the order of rules within a
+ * policy and bits edited by hand do not enter.
+ * kano_verdict_matrix: dst's rows := (verdict == allow), for the rows r0..r1
+ * both contexts hold; dst as kano_policy_subset's (same n, device and rows;
+ * every word of every held row is written; it then reads as an edited matrix;
+ * the rows of row shards concatenate).  Any number of distinct priorities.
+ * info (nullable) = [alive allow policies, alive deny policies, distinct
+ * priorities of the alive policies, row classes of src with an alive deny
+ * policy (a row shard classifies the rows it holds: its count is over those
+ * classes, and the counts of shards do not add up to the whole build's)].
+ * kano_pair_verdicts: verdict[q] = 0 none / 1 allow / 2 deny; decided_prio[q]
+ * (nullable) = t*, 0 where none; decider[q] (nullable) = the engine id, -1
+ * where none; counts (nullable) = [none, allow, deny] over the pairs whose i
+ * this context holds.  Pairs in any order, duplicates allowed.  On a row
+ * shard a pair whose i lies outside r0..r1 gets verdict 0 and decider -1 and
+ * adds to no count, so the verdicts of row shards combine by maximum and the
+ * counts add.
+ * -EINVAL: a NULL argument (pairs and verdict may be NULL with Q == 0;
+ * decided_prio, decider, counts and info always), src == dst, contexts of
+ * different n, device or rows, nids != P + added, an action byte > 1, Q < 0,
+ * a context holding policy lists, a context whose matrix has no policies (as
+ * kano_pair_policies); -ERANGE: a pair index outside [0, n); -ENOTSUP:
+ * kano_verdict_matrix over more than 1,048,560 row classes; -ENOMEM (with a
+ * message): a device buffer could not be allocated.  kano_verdict_matrix
+ * reports its errors on dst.  Q == 0, n == 0 or no held rows give empty or
+ * zero results and launch nothing.  Exact bits and integers.
+ * The device buffers are the call's own (the keys, the rank-ordered copy of
+ * the class lists, the class-level rows and their bit-transposed groups, the
+ * marked rows; the pairs and the results), freed on return: src's matrix
+ * (never read), its class tables and every stored check result are unchanged,
+ * a call between pipelined kano_verify steps leaves the next step's results
+ * unchanged, and the context stays usable after every error. */
+int kano_verdict_matrix(kano_ctx* src, kano_ctx* dst, int64_t nids,
+                        const int32_t* prio /* nids */,
+                        const uint8_t* action /* nids: 0 allow, 1 deny */,
+                        int64_t* info /* 4, nullable */);
+int kano_pair_verdicts(kano_ctx* ctx, int64_t Q, const int32_t* pairs /* 2*Q */,
+                       int64_t nids, const int32_t* prio, const uint8_t* action,
+                       uint8_t* verdict /* Q */, int32_t* decided_prio /* Q, nullable */,
+                       int32_t* decider /* Q, nullable */,
+                       int64_t* counts /* 3, nullable */);
+/* KANO_TUNE timing=1: the last call's device time in ms (the fills and the
+ * kernels, no copies; kano_verdict_matrix's on src and on dst alike), else 0.
+ * KANO_TUNE pvf=1/2 forces kano_pair_verdicts' lane / wave form, pvgrid=K caps
+ * its grid. */
+int kano_verdict_matrix_time(kano_ctx* ctx, float* ms);
+int kano_pair_verdicts_time(kano_ctx* ctx, float* ms);
+
 /* matrix_diff: what a change adds and removes.  a and b hold matrices of the
  * same n on the same device over the same rows r0..r1 (built, loaded, path or
  * edge matrices alike); for i in [r0, r1), j in [0, n):

@@ -173,6 +173,8 @@ struct kano_ctx {
   int pair_grid = 0;         // ppgrid=K: at most K blocks for k_pair_lane / k_pair_wave (0: 8 per CU)
   int pmask_form = 0;        // pmf=1/2: kano_pair_masks' lane / wave form forced (0: as pair_policies')
   int pmask_grid = 0;        // pmgrid=K: at most K blocks for k_pmask_lane / k_pmask_wave (0: 8 per CU)
+  int verdict_form = 0;      // pvf=1/2: kano_pair_verdicts' lane / wave form forced (0: as pair_policies')
+  int verdict_grid = 0;      // pvgrid=K: at most K blocks for k_verdict_lane / k_verdict_wave (0: 8 per CU)
   int diff_grid = 0;         // dgrid=K: at most K blocks for k_diff_rows (0: every resident block)
   int group_grid = 0;        // ggrid=K: at most K blocks for k_group_rows (0: every resident block)
   int group_batches = 0;     // gbatch=K: at most K batches of 64 destination groups in one
@@ -309,6 +311,11 @@ struct kano_ctx {
   // leaves its time on the source and on the destination)
   float subset_ms = 0.f;      // timing=1: the last kano_policy_subset's fills + kernels
   float pmask_ms = 0.f;       // timing=1: the last kano_pair_masks' kernel
+  // verdict_matrix / pair_verdicts (kano_verdict_matrix / kano_pair_verdicts):
+  // the device buffers are the call's own; only the times stay
+  // (kano_verdict_matrix leaves its time on the source and on the destination)
+  float verdict_ms = 0.f;     // timing=1: the last kano_verdict_matrix's fills + kernels
+  float pverdict_ms = 0.f;    // timing=1: the last kano_pair_verdicts' kernel
   // policy_shadow count-only (kano_verify with shadow_cap < 0): the grouped
   // count (k_shg_*) instead of the pair-by-pair flags
   bool vs_count_only = false;

@@ -11,6 +11,7 @@
 #include "kano_hops.hpp"
 #include "kano_intents.hpp"
 #include "kano_ports.hpp"
+#include "kano_verdict.hpp"
 
 using namespace kano_eng;
 
@@ -1691,6 +1692,17 @@ int kano_intents_time(kano_ctx* ctx, float* ms) {
 // ===========================================================================
 namespace {
 
+// the two events of a timing=1 call, destroyed also where the call fails
+// between their creation and its end
+struct EventPair {
+  hipEvent_t e[2] = {nullptr, nullptr};
+  hipEvent_t& operator[](int k) { return e[k]; }
+  ~EventPair() {
+    for (hipEvent_t x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
+};
+
 const char* const NO_POLICIES =
     ": the matrix has no policies (an empty, copied, loaded, path or edge matrix holds rows only)";
 
@@ -1750,7 +1762,7 @@ int kano_policy_subset(kano_ctx* src, kano_ctx* dst, int64_t nids, const uint8_t
       KTRY(dalloc(ctx, mcs, sizeof(u64) * (size_t)(U * ldC)));
       KTRY(dalloc(ctx, rt16, sizeof(uint16_t) * (size_t)(((U + 15) / 16) * Ua)));
     }
-    hipEvent_t tev[2] = {nullptr, nullptr};
+    EventPair tev;
     if (src->stage_timing || dst->stage_timing) {
       KCHK(hipEventCreate(&tev[0]));
       KCHK(hipEventCreate(&tev[1]));
@@ -1784,8 +1796,6 @@ int kano_policy_subset(kano_ctx* src, kano_ctx* dst, int64_t nids, const uint8_t
       float ms = 0.f;
       (void)hipEventElapsedTime(&ms, tev[0], tev[1]);
       src->subset_ms = dst->subset_ms = ms;
-      (void)hipEventDestroy(tev[0]);
-      (void)hipEventDestroy(tev[1]);
     }
     KCHK(hipMemcpyAsync(&kept_classes, cnt.p, sizeof(unsigned), hipMemcpyDeviceToHost,
                         ctx->stream));
@@ -1877,7 +1887,7 @@ int kano_pair_masks(kano_ctx* ctx, int64_t Q, const int32_t* pairs, int64_t nids
     const i64 cap = ctx->pmask_grid > 0 ? ctx->pmask_grid : (i64)std::max(1, ctx->num_cus) * 8;
     const unsigned grid =
         (unsigned)std::min<i64>(cap, wave ? (Q + TPB / 64 - 1) / (TPB / 64) : nblk(Q));
-    hipEvent_t tev[2] = {nullptr, nullptr};
+    EventPair tev;
     if (ctx->stage_timing) {
       KCHK(hipEventCreate(&tev[0]));
       KCHK(hipEventCreate(&tev[1]));
@@ -1890,8 +1900,6 @@ int kano_pair_masks(kano_ctx* ctx, int64_t Q, const int32_t* pairs, int64_t nids
       KCHK(hipEventRecord(tev[1], ctx->stream));
       KCHK(hipEventSynchronize(tev[1]));
       (void)hipEventElapsedTime(&ctx->pmask_ms, tev[0], tev[1]);
-      (void)hipEventDestroy(tev[0]);
-      (void)hipEventDestroy(tev[1]);
     }
     KCHK(hipMemcpyAsync(out, od.p, b_out, hipMemcpyDeviceToHost, ctx->stream));
     return sync(ctx);
@@ -1911,6 +1919,332 @@ int kano_policy_subset_time(kano_ctx* ctx, float* ms) {
 int kano_pair_masks_time(kano_ctx* ctx, float* ms) {
   if (!ctx || !ms) return -EINVAL;
   *ms = ctx->pmask_ms;
+  return 0;
+}
+
+}  // extern "C"
+
+// ===========================================================================
+// verdict_matrix / pair_verdicts: deny rules and priorities over the resident
+// tables (k_verdict_*, kano_verdict.hpp; the class rows' expansion is
+// kano_path's, path_expand_rows; the rows of the added policies are marked by
+// k_inc_mark).  The matrix of the source is not read and nothing of the source
+// is written.
+// ===========================================================================
+namespace {
+
+// The keys of the engine ids (kano_verdict.hpp: rank * 2 + action, VD_DEAD
+// for a removed id) from the raw priorities: the rank is the position among
+// the distinct priorities of the alive ids, ascending; levels[rank] gives the
+// priority back.  tally = [alive allow, alive deny].
+int verdict_keys(kano_ctx* src, kano_ctx* ctx, const char* what, i64 nids, const int32_t* prio,
+                 const uint8_t* action, std::vector<uint32_t>& key, std::vector<int32_t>& levels,
+                 i64 tally[2]) {
+  for (i64 p = 0; p < nids; ++p)
+    if (action[p] > 1)
+      return fail(ctx, -EINVAL, std::string(what) + ": action " + std::to_string(p) + " is " +
+                                    std::to_string((int)action[p]) + " (0 allow, 1 deny)");
+  levels.clear();
+  for (i64 p = 0; p < nids; ++p)
+    if (!src->dead[p]) levels.push_back(prio[p]);
+  std::sort(levels.begin(), levels.end());
+  levels.erase(std::unique(levels.begin(), levels.end()), levels.end());
+  key.assign((size_t)nids, kano::VD_DEAD);
+  tally[0] = tally[1] = 0;
+  for (i64 p = 0; p < nids; ++p) {
+    if (src->dead[p]) continue;
+    const uint32_t rank =
+        (uint32_t)(std::lower_bound(levels.begin(), levels.end(), prio[p]) - levels.begin());
+    key[p] = rank * 2u + action[p];
+    ++tally[action[p]];
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kano_verdict_matrix(kano_ctx* src, kano_ctx* dst, int64_t nids, const int32_t* prio,
+                        const uint8_t* action, int64_t* info) {
+  if (!src || !dst) return -EINVAL;
+  if (src == dst)
+    return fail(dst, -EINVAL, "kano_verdict_matrix: the destination must be another context");
+  if (src->device != dst->device)
+    return fail(dst, -EINVAL, "kano_verdict_matrix: contexts on two devices");
+  kano_ctx* ctx = dst;
+  KCHK(hipSetDevice(dst->device));
+  {
+    const int rc = ensure_built(src);
+    if (rc) return fail(dst, rc, "kano_verdict_matrix: source: " + src->err);
+  }
+  if (src->lists_mode)
+    return fail(dst, -EINVAL, "kano_verdict_matrix: the source holds policy lists, not a matrix");
+  const i64 P = src->P, A = src->inc_A;
+  if (P == 0 && A == 0) return fail(dst, -EINVAL, std::string("kano_verdict_matrix") + NO_POLICIES);
+  if (nids != P + A)
+    return fail(dst, -EINVAL, "kano_verdict_matrix: nids = " + std::to_string(nids) +
+                                  ", the source has " + std::to_string(P + A) + " engine ids");
+  if (!prio || !action) return fail(dst, -EINVAL, "kano_verdict_matrix: prio or action is NULL");
+  KTRY(ensure_matrix(dst));
+  if (dst->n != src->n || dst->r0 != src->r0 || dst->r1 != src->r1 || dst->ldM != src->ldM)
+    return fail(dst, -EINVAL, "kano_verdict_matrix: the destination must hold the same rows of a "
+                              "matrix of the same size");
+  {
+    const int rc = sync(src);   // the source's classes are complete
+    if (rc) return fail(dst, rc, "kano_verdict_matrix: source: " + src->err);
+  }
+  std::vector<uint32_t> key;
+  std::vector<int32_t> levels;
+  i64 tally[2];
+  KTRY(verdict_keys(src, dst, "kano_verdict_matrix", nids, prio, action, key, levels, tally));
+  // aflag[P + t]: added policy t is alive (k_inc_mark's flags; the build's stay 0)
+  std::vector<uint8_t> aflag((size_t)nids, 0);
+  i64 alive_added = 0;
+  for (i64 t = 0; t < A; ++t) alive_added += aflag[P + t] = !src->dead[P + t];
+  const i64 n = dst->n, W = dst->W, ldM = dst->ldM, r0 = dst->r0, rl = rows_local(dst);
+  const i64 U = src->rc.U, Ua = src->cc.U, ldC = src->ldC;
+  const bool classes = P > 0 && U > 0 && Ua > 0;
+  if (classes && (U + 15) / 16 > 65535)
+    return fail(dst, -ENOTSUP, "kano_verdict_matrix: more than 1,048,560 row classes");
+  src->verdict_ms = dst->verdict_ms = 0.f;
+  unsigned deny_classes = 0;
+  DBuf keyd, flagd, cnt, pk, olist, okey, ocnt, vc, rt16, mrows;
+  auto run = [&]() -> int {
+    KTRY(dalloc(ctx, keyd, sizeof(uint32_t) * (size_t)nids));
+    KTRY(dalloc(ctx, cnt, 2 * sizeof(u64)));   // [0]: the marked rows, [1]: the deny classes
+    KCHK(hipMemcpyAsync(keyd.p, key.data(), sizeof(uint32_t) * (size_t)nids, hipMemcpyHostToDevice,
+                        ctx->stream));
+    if (classes) {
+      const size_t nnz = (size_t)std::max<i64>(1, src->nnz_sel);
+      KTRY(dalloc(ctx, pk, sizeof(u64) * nnz));
+      KTRY(dalloc(ctx, olist, sizeof(int32_t) * nnz));
+      KTRY(dalloc(ctx, okey, sizeof(uint32_t) * nnz));
+      KTRY(dalloc(ctx, ocnt, sizeof(int32_t) * (size_t)U));
+      KTRY(dalloc(ctx, vc, sizeof(u64) * (size_t)(U * ldC)));
+      KTRY(dalloc(ctx, rt16, sizeof(uint16_t) * (size_t)(((U + 15) / 16) * Ua)));
+    }
+    if (alive_added > 0) {
+      KTRY(dalloc(ctx, flagd, (size_t)nids));
+      KTRY(dalloc(ctx, mrows, sizeof(int32_t) * (size_t)rl));
+      KCHK(hipMemcpyAsync(flagd.p, aflag.data(), (size_t)nids, hipMemcpyHostToDevice, ctx->stream));
+    }
+    EventPair tev;
+    if (src->stage_timing || dst->stage_timing) {
+      KCHK(hipEventCreate(&tev[0]));
+      KCHK(hipEventCreate(&tev[1]));
+      KCHK(hipEventRecord(tev[0], ctx->stream));
+    }
+    KCHK(hipMemsetAsync(cnt.p, 0, 2 * sizeof(u64), ctx->stream));
+    const uint32_t* key_d = P_<uint32_t>(keyd);
+    if (classes) {
+      int wl = 1;
+      while (wl < TPB && wl < ldC) wl <<= 1;
+      const i64 cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
+      hipLaunchKernelGGL(k_verdict_order, dim3((unsigned)std::min<i64>(U, cus * 8)), dim3(TPB), 0,
+                         ctx->stream, U, (const i64*)P_<i64>(src->soffc),
+                         (const int32_t*)P_<int32_t>(src->slist), key_d, P_<u64>(pk),
+                         P_<int32_t>(olist),
+                         P_<uint32_t>(okey), P_<int32_t>(ocnt),
+                         reinterpret_cast<unsigned*>(P_<u64>(cnt) + 1));
+      KLAUNCH();
+      const i64 cpb = TPB / wl;
+      hipLaunchKernelGGL(k_verdict_class, dim3((unsigned)std::min<i64>((U + cpb - 1) / cpb, cus * 8)),
+                         dim3(TPB), 0, ctx->stream, U, (const i64*)P_<i64>(src->soffc),
+                         (const int32_t*)P_<int32_t>(olist), (const uint32_t*)P_<uint32_t>(okey),
+                         (const int32_t*)P_<int32_t>(ocnt), (const u64*)P_<u64>(src->AC), ldC, wl,
+                         P_<u64>(vc));
+      KLAUNCH();
+      // the class rows to the member rows: every word of every held row
+      KTRY(path_expand_rows(ctx, src, P_<u64>(vc), ldC, U, Ua, rt16.p));
+    } else {
+      // a build without policies has no classes: the rows start as zeros
+      KCHK(hipMemsetAsync(dst->M.p, 0, sizeof(u64) * (size_t)(rl * ldM), ctx->stream));
+    }
+    if (alive_added > 0) {
+      // the rows an alive added policy selects, resolved bit by bit
+      hipLaunchKernelGGL(k_inc_mark, dim3(nblk(rl)), dim3(TPB), 0, ctx->stream,
+                         (const int32_t*)nullptr, (const i64*)nullptr, (const int32_t*)nullptr,
+                         (const uint8_t*)P_<uint8_t>(flagd), P, (const u64*)P_<u64>(src->asel), W,
+                         A, r0, rl, P_<int32_t>(mrows), P_<u64>(cnt));
+      KLAUNCH();
+      u64 nrows = 0;
+      KCHK(hipMemcpyAsync(&nrows, cnt.p, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+      KTRY(sync(ctx));
+      if (nrows > (u64)rl) return fail(ctx, -EIO, "kano_verdict_matrix: row count out of range");
+      if (nrows > 0) {
+        VerdictArgs a{};
+        a.rcls = classes ? P_<int32_t>(src->rc.cls) : nullptr;
+        a.ccls = P_<int32_t>(src->cc.cls);
+        a.soffc = P_<i64>(src->soffc);
+        a.slist = P_<int32_t>(src->slist);
+        a.key = key_d;
+        a.AC = P_<u64>(src->AC);
+        a.ldC = ldC;
+        a.P = P;
+        a.asel = P_<u64>(src->asel);
+        a.aalw = P_<u64>(src->aalw);
+        a.W = W;
+        a.A = A;
+        a.r0 = r0;
+        a.r1 = dst->r1;
+        hipLaunchKernelGGL(k_verdict_rows, dim3((unsigned)nrows), dim3(TPB), 0, ctx->stream, a,
+                           (const int32_t*)P_<int32_t>(mrows), n, P_<u64>(dst->M), ldM);
+        KLAUNCH();
+      }
+    }
+    if (tev[0]) {
+      KCHK(hipEventRecord(tev[1], ctx->stream));
+      KCHK(hipEventSynchronize(tev[1]));
+      float ms = 0.f;
+      (void)hipEventElapsedTime(&ms, tev[0], tev[1]);
+      src->verdict_ms = dst->verdict_ms = ms;
+    }
+    KCHK(hipMemcpyAsync(&deny_classes, P_<u64>(cnt) + 1, sizeof(unsigned), hipMemcpyDeviceToHost,
+                        ctx->stream));
+    return sync(ctx);
+  };
+  int rc = 0;
+  if (n > 0 && rl > 0) {
+    rc = run();
+    if (rc) (void)hipStreamSynchronize(ctx->stream);   // nothing in flight on the temporaries
+    for (DBuf* b : {&keyd, &flagd, &cnt, &pk, &olist, &okey, &ocnt, &vc, &rt16, &mrows}) dfree(*b);
+    dst->cols_valid = false;
+    dst->rows_dirty = true;
+    dst->user_edited = true;
+  }
+  if (rc) return rc;
+  if (info) {
+    info[0] = tally[0];
+    info[1] = tally[1];
+    info[2] = (int64_t)levels.size();
+    info[3] = (int64_t)deny_classes;
+  }
+  return 0;
+}
+
+int kano_pair_verdicts(kano_ctx* ctx, int64_t Q, const int32_t* pairs, int64_t nids,
+                       const int32_t* prio, const uint8_t* action, uint8_t* verdict,
+                       int32_t* decided_prio, int32_t* decider, int64_t* counts) {
+  KTRY(ensure_built(ctx));
+  if (ctx->lists_mode)
+    return fail(ctx, -EINVAL, "kano_pair_verdicts: the context holds policy lists, not a matrix");
+  const i64 P = ctx->P, A = ctx->inc_A;
+  if (P == 0 && A == 0) return fail(ctx, -EINVAL, std::string("kano_pair_verdicts") + NO_POLICIES);
+  if (Q < 0) return fail(ctx, -EINVAL, "kano_pair_verdicts: Q < 0");
+  if (nids != P + A)
+    return fail(ctx, -EINVAL, "kano_pair_verdicts: nids = " + std::to_string(nids) +
+                                  ", the context has " + std::to_string(P + A) + " engine ids");
+  if (!prio || !action || (Q > 0 && (!pairs || !verdict)))
+    return fail(ctx, -EINVAL, "kano_pair_verdicts: pairs, prio, action or verdict is NULL");
+  std::vector<uint32_t> key;
+  std::vector<int32_t> levels;
+  i64 tally[2];
+  KTRY(verdict_keys(ctx, ctx, "kano_pair_verdicts", nids, prio, action, key, levels, tally));
+  const i64 n = ctx->n;
+  for (i64 q = 0; q < Q; ++q)
+    if (pairs[2 * q] < 0 || pairs[2 * q] >= n || pairs[2 * q + 1] < 0 || pairs[2 * q + 1] >= n)
+      return fail(ctx, -ERANGE, "kano_pair_verdicts: pair " + std::to_string(q) + " out of range");
+  ctx->pverdict_ms = 0.f;
+  if (counts) counts[0] = counts[1] = counts[2] = 0;
+  if (Q == 0) return 0;
+  auto none = [&]() {
+    std::memset(verdict, 0, (size_t)Q);
+    if (decided_prio) std::memset(decided_prio, 0, sizeof(int32_t) * (size_t)Q);
+    if (decider) std::fill(decider, decider + Q, -1);
+  };
+  if (rows_local(ctx) <= 0) {
+    none();
+    return 0;
+  }
+  std::vector<uint32_t> hkey((size_t)Q);
+  std::vector<int32_t> hid((size_t)Q);
+  DBuf pr, kd, ok, oi;
+  auto run = [&]() -> int {
+    KTRY(dalloc(ctx, pr, sizeof(int32_t) * 2 * (size_t)Q));
+    KTRY(dalloc(ctx, kd, sizeof(uint32_t) * (size_t)nids));
+    KTRY(dalloc(ctx, ok, sizeof(uint32_t) * (size_t)Q));
+    KTRY(dalloc(ctx, oi, sizeof(int32_t) * (size_t)Q));
+    KCHK(hipMemcpyAsync(pr.p, pairs, sizeof(int32_t) * 2 * (size_t)Q, hipMemcpyHostToDevice,
+                        ctx->stream));
+    KCHK(hipMemcpyAsync(kd.p, key.data(), sizeof(uint32_t) * (size_t)nids, hipMemcpyHostToDevice,
+                        ctx->stream));
+    VerdictArgs a{};
+    a.pairs = P_<int32_t>(pr);
+    a.Q = Q;
+    // (a build without policies has no classes: only the added part remains)
+    a.rcls = P > 0 && ctx->rc.U > 0 ? P_<int32_t>(ctx->rc.cls) : nullptr;
+    a.ccls = P_<int32_t>(ctx->cc.cls);
+    a.soffc = P_<i64>(ctx->soffc);
+    a.slist = P_<int32_t>(ctx->slist);
+    a.key = P_<uint32_t>(kd);
+    a.AC = P_<u64>(ctx->AC);
+    a.ldC = ctx->ldC;
+    a.P = P;
+    a.asel = P_<u64>(ctx->asel);
+    a.aalw = P_<u64>(ctx->aalw);
+    a.W = ctx->W;
+    a.A = A;
+    a.r0 = ctx->r0;
+    a.r1 = ctx->r1;
+    a.out_key = P_<uint32_t>(ok);
+    a.out_id = P_<int32_t>(oi);
+    if (a.rcls && !a.ccls) return fail(ctx, -EINVAL, "kano_pair_verdicts: no column classes");
+    // the form as kano_pair_masks picks it: by the mean list a pair walks
+    const i64 U = ctx->rc.U;
+    const i64 sbar = (a.rcls ? (ctx->nnz_sel + U - 1) / U : 0) + A;
+    bool wave = sbar > VERDICT_WAVE_MIN;
+    if (ctx->verdict_form) wave = ctx->verdict_form == 2;
+    const i64 cap = ctx->verdict_grid > 0 ? ctx->verdict_grid : (i64)std::max(1, ctx->num_cus) * 8;
+    const unsigned grid =
+        (unsigned)std::min<i64>(cap, wave ? (Q + TPB / 64 - 1) / (TPB / 64) : nblk(Q));
+    EventPair tev;
+    if (ctx->stage_timing) {
+      KCHK(hipEventCreate(&tev[0]));
+      KCHK(hipEventCreate(&tev[1]));
+      KCHK(hipEventRecord(tev[0], ctx->stream));
+    }
+    if (wave) hipLaunchKernelGGL(k_verdict_wave, dim3(grid), dim3(TPB), 0, ctx->stream, a);
+    else hipLaunchKernelGGL(k_verdict_lane, dim3(grid), dim3(TPB), 0, ctx->stream, a);
+    KLAUNCH();
+    if (tev[0]) {
+      KCHK(hipEventRecord(tev[1], ctx->stream));
+      KCHK(hipEventSynchronize(tev[1]));
+      (void)hipEventElapsedTime(&ctx->pverdict_ms, tev[0], tev[1]);
+    }
+    KCHK(hipMemcpyAsync(hkey.data(), ok.p, sizeof(uint32_t) * (size_t)Q, hipMemcpyDeviceToHost,
+                        ctx->stream));
+    KCHK(hipMemcpyAsync(hid.data(), oi.p, sizeof(int32_t) * (size_t)Q, hipMemcpyDeviceToHost,
+                        ctx->stream));
+    return sync(ctx);
+  };
+  const int rc = run();
+  if (rc) (void)hipStreamSynchronize(ctx->stream);   // nothing in flight on the temporaries
+  for (DBuf* b : {&pr, &kd, &ok, &oi}) dfree(*b);
+  if (rc) return rc;
+  // the keys back to verdicts and raw priorities; a pair whose i this context
+  // does not hold matched nothing and adds to no count
+  for (i64 q = 0; q < Q; ++q) {
+    const bool own = pairs[2 * q] >= ctx->r0 && pairs[2 * q] < ctx->r1;
+    const bool hit = hkey[q] != VD_NONE;
+    const int v = !hit ? 0 : (hkey[q] & 1u) ? 2 : 1;
+    verdict[q] = (uint8_t)v;
+    if (decided_prio) decided_prio[q] = hit ? levels[hkey[q] >> 1] : 0;
+    if (decider) decider[q] = hit ? hid[q] : -1;
+    if (counts && own) ++counts[v];
+  }
+  return 0;
+}
+
+int kano_verdict_matrix_time(kano_ctx* ctx, float* ms) {
+  if (!ctx || !ms) return -EINVAL;
+  *ms = ctx->verdict_ms;
+  return 0;
+}
+
+int kano_pair_verdicts_time(kano_ctx* ctx, float* ms) {
+  if (!ctx || !ms) return -EINVAL;
+  *ms = ctx->pverdict_ms;
   return 0;
 }
 

@@ -2348,6 +2348,8 @@ int kano_create(int device, kano_ctx** out) {
         if (k == "ppgrid" && v >= 0) ctx->pair_grid = v;
         if (k == "pmf" && v >= 0 && v <= 2) ctx->pmask_form = v;
         if (k == "pmgrid" && v >= 0) ctx->pmask_grid = v;
+        if (k == "pvf" && v >= 0 && v <= 2) ctx->verdict_form = v;
+        if (k == "pvgrid" && v >= 0) ctx->verdict_grid = v;
         if (k == "dgrid" && v >= 0) ctx->diff_grid = v;
         if (k == "ggrid" && v >= 0) ctx->group_grid = v;
         if (k == "gbatch" && v >= 0) ctx->group_batches = v;

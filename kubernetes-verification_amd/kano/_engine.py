@@ -701,6 +701,61 @@ class DeviceBuild:
         self._chk(self.lib.kano_pair_masks_time(self.ctx, byref(ms)), "kano_pair_masks_time")
         return float(ms.value)
 
+    # -- verdict_matrix / pair_verdicts (kano_verdict_matrix / kano_pair_verdicts)
+    @staticmethod
+    def _tiers(prio, action):
+        """int32 priorities and uint8 actions (0 allow, 1 deny), one per engine id."""
+        pr = np.ascontiguousarray(np.asarray(prio).reshape(-1), dtype=np.int32)
+        ac = np.ascontiguousarray(np.asarray(action).reshape(-1), dtype=np.uint8)
+        if pr.shape != ac.shape:
+            raise ValueError(f"{pr.shape[0]} priorities for {ac.shape[0]} actions")
+        return pr, ac
+
+    def verdict_into(self, dst: "DeviceBuild", prio, action) -> dict:
+        """dst's rows := the pairs whose verdict is allow (kano_verdict_matrix):
+        ``prio`` (int32: a smaller number is evaluated first) and ``action``
+        (0 allow, 1 deny) hold one entry per engine id (the build's, then the
+        added ones; removed ids are ignored).  ``dst`` as subset_into's; this
+        context's matrix and tables are not written."""
+        pr, ac = self._tiers(prio, action)
+        info = np.zeros(4, dtype=np.int64)
+        dst._chk(self.lib.kano_verdict_matrix(self.ctx, dst.ctx, int(pr.shape[0]), _ptr(pr),
+                                              _ptr(ac), _ptr(info)), "kano_verdict_matrix")
+        return dict(zip(("allow_policies", "deny_policies", "levels", "deny_classes"),
+                        map(int, info)))
+
+    def pair_verdicts(self, pairs, prio, action) -> dict:
+        """The verdict of each pod pair of ``pairs`` (kano_pair_verdicts):
+        ``verdict`` (uint8: 0 none, 1 allow, 2 deny), ``priority`` (int32: the
+        deciding priority, 0 where none), ``policy`` (int32: the deciding
+        engine id, -1 where none) and ``counts`` (int64: none, allow, deny over
+        the pairs whose i this context holds).  A row shard answers for the
+        pairs whose i it holds (the others get verdict 0 and policy -1)."""
+        pairs, Q = _as_pairs(pairs)
+        pr, ac = self._tiers(prio, action)
+        verdict = np.zeros(Q, dtype=np.uint8)
+        priority = np.zeros(Q, dtype=np.int32)
+        policy = np.full(Q, -1, dtype=np.int32)
+        counts = np.zeros(3, dtype=np.int64)
+        self._chk(self.lib.kano_pair_verdicts(self.ctx, Q, _ptr(pairs), int(pr.shape[0]), _ptr(pr),
+                                              _ptr(ac), _ptr(verdict), _ptr(priority),
+                                              _ptr(policy), _ptr(counts)), "kano_pair_verdicts")
+        return dict(verdict=verdict, priority=priority, policy=policy, counts=counts)
+
+    def verdict_time(self) -> float:
+        """The last verdict_into's device time (ms; KANO_TUNE=timing=1)."""
+        ms = ctypes.c_float(0.0)
+        self._chk(self.lib.kano_verdict_matrix_time(self.ctx, byref(ms)),
+                  "kano_verdict_matrix_time")
+        return float(ms.value)
+
+    def pair_verdicts_time(self) -> float:
+        """The last pair_verdicts' device time (ms; KANO_TUNE=timing=1)."""
+        ms = ctypes.c_float(0.0)
+        self._chk(self.lib.kano_pair_verdicts_time(self.ctx, byref(ms)),
+                  "kano_pair_verdicts_time")
+        return float(ms.value)
+
     # -- matrix_diff (kano_diff / kano_diff_pairs / kano_copy_matrix) -----
     DIFF_KINDS = {"added": 0, "removed": 1}
 

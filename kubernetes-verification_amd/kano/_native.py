@@ -69,6 +69,11 @@ SIGNATURES = {
                                 c_void_p]),
     "kano_policy_subset_time": (c_int, [c_void_p, POINTER(c_float)]),
     "kano_pair_masks_time": (c_int, [c_void_p, POINTER(c_float)]),
+    "kano_verdict_matrix": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "kano_pair_verdicts": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p]),
+    "kano_verdict_matrix_time": (c_int, [c_void_p, POINTER(c_float)]),
+    "kano_pair_verdicts_time": (c_int, [c_void_p, POINTER(c_float)]),
     "kano_diff": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "kano_diff_pairs": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64,
                                 POINTER(c_int64), c_void_p]),

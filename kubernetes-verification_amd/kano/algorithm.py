@@ -921,3 +921,144 @@ def port_exposure(matrix: ReachabilityMatrix) -> Tuple[list, np.ndarray]:
     finally:
         out._engine.close()
     return t.keys, counts
+
+
+# ---------------------------------------------------------------------------
+# Deny rules and tiers.  Not part of kano_py, whose policies only allow.  Over
+# the working sets of the matrix's current policies every policy p carries an
+# action (allow / deny) and an integer priority, a smaller number evaluated
+# first (kano/verdicts.py: attributes set on the Policy objects, or an
+# explicit Tiering).  p matches (i, j) iff i in select_p and j in allow_p;
+# with t*(i, j) the smallest priority over the matching policies,
+#   verdict(i, j) = none   nothing matches (unreachable: kano's reading)
+#                   deny   some deny policy of priority t* matches (within one
+#                          priority deny wins)
+#                   allow  otherwise
+#   verdict_matrix[i, j] = 1 iff verdict(i, j) = allow
+# and the deciding policy is the smallest current index among the matching
+# policies of priority t* with the winning action.  Computed on the device
+# from the resident tables (kano_verdict_matrix / kano_pair_verdicts) without
+# touching the matrix, for built and incrementally updated matrices alike.
+# All-allow with any priorities is the built matrix; one priority for all is
+# subset(allows) & ~subset(denies).  A verdict matrix is a rows-only
+# ReachabilityMatrix like a subset matrix: every check above, matrix_diff,
+# hop_*, group_reachability and check_intents read it.  Pass, the order of
+# rules within a policy, YAML for AdminNetworkPolicy objects, bits edited by
+# hand and the accumulated lists of quirk Q5 do not enter.
+
+from .verdicts import ALLOW, DENY, VERDICT_NAMES, Tiering, tiering  # noqa: E402,F401
+from . import verdicts as _verdicts  # noqa: E402
+
+
+class PairVerdicts(NamedTuple):
+    verdict: np.ndarray        # uint8 per queried pair: 0 none, 1 allow, 2 deny
+    priority: np.ndarray       # int32: the deciding priority t* (0 where none)
+    policy: np.ndarray         # int32: the deciding policy's current index, -1 where none
+
+    def allowed(self) -> np.ndarray:
+        """bool (Q,): the queried pairs whose verdict is allow."""
+        return self.verdict == 1
+
+    def denied(self) -> np.ndarray:
+        """bool (Q,): the queried pairs a deny policy decides."""
+        return self.verdict == 2
+
+    def of(self, q: int) -> Tuple[str, Optional[int], Optional[int]]:
+        """("allow" | "deny" | "none", priority or None, policy or None) of
+        queried pair q."""
+        q = int(q)
+        if not -len(self.verdict) <= q < len(self.verdict):
+            raise IndexError("pair index out of range")
+        v = int(self.verdict[q])
+        if v == 0:
+            return "none", None, None
+        return VERDICT_NAMES[v], int(self.priority[q]), int(self.policy[q])
+
+
+def _engine_tiers(matrix: ReachabilityMatrix, eng, ids, tiers) -> Tuple[np.ndarray, np.ndarray]:
+    """(priorities, actions) over the engine ids from the tiers of the current
+    policies (the entries of removed ids stay 0: the engine ignores them)."""
+    t = _verdicts.resolve(matrix._policies, tiers)
+    prio = np.zeros(eng.nids(), dtype=np.int32)
+    act = np.zeros(eng.nids(), dtype=np.uint8)
+    at = np.arange(len(t)) if ids is None else ids[0]
+    prio[at] = t.priorities
+    act[at] = t.actions
+    return prio, act
+
+
+def verdict_matrix(matrix: ReachabilityMatrix, tiers=None) -> ReachabilityMatrix:
+    """The pairs whose verdict is allow under the tiers (default: the ones the
+    current policies carry, kano.verdicts.tiering), written on the device from
+    the resident tables into a new rows-only matrix; ``verdict_info`` holds the
+    alive allow and deny policies, the distinct priorities and the row classes
+    with a deny policy."""
+    eng, _, ids, P = _pair_engine(matrix, [])
+    prio, act = _engine_tiers(matrix, eng, ids, tiers)
+    out = _empty_like(matrix)
+    out.verdict_info = dict(allow_policies=0, deny_policies=0, levels=0, deny_classes=0)
+    if P and matrix.container_size:
+        try:
+            out.verdict_info = eng.verdict_into(out._engine, prio, act)
+        except BaseException:
+            out._engine.close()
+            raise
+    return out
+
+
+def pair_verdicts(matrix: ReachabilityMatrix, pairs, tiers=None) -> PairVerdicts:
+    """For every (i, j) of ``pairs`` the verdict, the deciding priority and the
+    deciding policy (see PairVerdicts); a matrix holding a row shard answers
+    for the pairs whose i it holds (the others get none)."""
+    eng, pr, ids, P = _pair_engine(matrix, pairs)
+    prio, act = _engine_tiers(matrix, eng, ids, tiers)
+    Q = pr.shape[0]
+    if P == 0 or Q == 0:
+        return PairVerdicts(np.zeros(Q, np.uint8), np.zeros(Q, np.int32), np.full(Q, -1, np.int32))
+    r = eng.pair_verdicts(pr, prio, act)
+    pol = r["policy"]
+    if ids is not None:
+        pol = np.where(pol >= 0, ids[1][np.maximum(pol, 0)], -1).astype(np.int32)
+    return PairVerdicts(r["verdict"], r["priority"], pol)
+
+
+def pair_verdict(matrix: ReachabilityMatrix, i: int, j: int,
+                 tiers=None) -> Tuple[str, Optional[int], Optional[int]]:
+    """("allow" | "deny" | "none", priority or None, policy or None) of (i, j)."""
+    return pair_verdicts(matrix, [(int(i), int(j))], tiers).of(0)
+
+
+def why_blocked(matrix: ReachabilityMatrix, i: int, j: int, tiers=None) -> List[int]:
+    """The ascending current indices of all deny policies of priority t* that
+    match (i, j); [] when the pair is allowed or unmatched.  (pair_policies'
+    list of the pair, filtered on the host.)"""
+    hit = pair_policies(matrix, [(int(i), int(j))]).of(0)
+    t = _verdicts.resolve(matrix._policies, tiers)      # (checked also where nothing matches)
+    if not hit:
+        return []
+    best = min(int(t.priorities[p]) for p in hit)
+    return [p for p in hit if int(t.priorities[p]) == best and t.actions[p] == DENY]
+
+
+def verdict_counts(matrix: ReachabilityMatrix, tiers=None) -> Dict[str, int]:
+    """{"allowed", "denied", "unmatched"}: the pod pairs of the held rows by
+    verdict (the counts of row shards add up).  The verdict matrix and the
+    matrix of all current policies are written into one reused destination and
+    counted on the device, the way port_exposure counts."""
+    eng, _, ids, P = _pair_engine(matrix, [])
+    prio, act = _engine_tiers(matrix, eng, ids, tiers)
+    n = matrix.container_size
+    r0, r1 = getattr(eng, "row_span", None) or (0, n)
+    total = (r1 - r0) * n
+    if P == 0 or n == 0:
+        return dict(allowed=0, denied=0, unmatched=total)
+    out = _empty_like(matrix)
+    try:
+        z = np.zeros(n, dtype=np.int32)
+        eng.verdict_into(out._engine, prio, act)
+        allowed = int(out._engine.group_counts(z, z, 1, 1)["counts"][0, 0])
+        eng.subset_into(out._engine, _engine_keep(eng, ids, range(P), P))
+        matched = int(out._engine.group_counts(z, z, 1, 1)["counts"][0, 0])
+    finally:
+        out._engine.close()
+    return dict(allowed=allowed, denied=matched - allowed, unmatched=total - matched)

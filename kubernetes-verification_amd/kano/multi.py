@@ -365,6 +365,31 @@ class MultiBuild:
         pair is answered by the member holding its i, the others give 0)."""
         return np.bitwise_or.reduce([m.pair_masks(pairs, pmask) for m in self.members])
 
+    def verdict_into(self, dst: "MultiBuild", prio, action) -> dict:
+        """DeviceBuild.verdict_into member by member: every member writes its
+        own rows of dst (a group over the same devices and row shards).
+        ``deny_classes`` is the sum over the members: a member classifies the
+        rows it holds, so a row class with pods in several shards counts once
+        in each (at least the whole build's count, not equal to it)."""
+        self._same_shards(dst, "verdict_into")
+        parts = [m.verdict_into(d, prio, action) for m, d in zip(self.members, dst.members)]
+        out = dict(parts[0])
+        out["deny_classes"] = sum(p["deny_classes"] for p in parts)
+        return out
+
+    def pair_verdicts(self, pairs, prio, action) -> dict:
+        """DeviceBuild.pair_verdicts over all rows: a pair is answered by the
+        member holding its i (the others give verdict 0 and policy -1), so the
+        members' arrays combine by maximum and their counts add."""
+        parts = [m.pair_verdicts(pairs, prio, action) for m in self.members]
+        verdict = np.maximum.reduce([p["verdict"] for p in parts])
+        owner = np.argmax([p["verdict"] for p in parts], axis=0)
+        q = np.arange(verdict.shape[0])
+        return dict(verdict=verdict,
+                    priority=np.stack([p["priority"] for p in parts])[owner, q],
+                    policy=np.stack([p["policy"] for p in parts])[owner, q],
+                    counts=np.sum([p["counts"] for p in parts], axis=0, dtype=np.int64))
+
     # -- matrix access: owners --------------------------------------------
     def rows(self, r0: int, nrows: int, out: Optional[np.ndarray] = None) -> np.ndarray:
         if out is None:
