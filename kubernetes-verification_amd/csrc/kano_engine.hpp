@@ -27,6 +27,7 @@
 
 #include "kano_hip.h"
 #include "kano_internal.hpp"
+#include "kano_pairwalk.hpp"
 #include "kano_prims.hpp"
 
 using namespace kano;
@@ -467,6 +468,44 @@ int sync(kano_ctx* ctx);
 int ensure_built(kano_ctx* ctx);
 int ensure_matrix(kano_ctx* ctx);
 i64 rows_local(const kano_ctx* ctx);
+
+// The events of a timing=1 call, destroyed also where the call fails between
+// their creation and its end.  start / stop bracket one stretch of the stream:
+// start creates the events and records the first, stop (nothing without a
+// start) records the last, waits for it and gives the time from [0] to [1].
+template <int N = 2>
+struct EventPair {
+  hipEvent_t e[N] = {};
+  hipEvent_t& operator[](int k) { return e[k]; }
+  ~EventPair() {
+    for (hipEvent_t x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
+  int start(kano_ctx* ctx) {
+    for (hipEvent_t& x : e) KCHK(hipEventCreate(&x));
+    KCHK(hipEventRecord(e[0], ctx->stream));
+    return 0;
+  }
+  int stop(kano_ctx* ctx, float* ms) {
+    if (!e[0]) return 0;
+    KCHK(hipEventRecord(e[1], ctx->stream));
+    KCHK(hipEventSynchronize(e[1]));
+    (void)hipEventElapsedTime(ms, e[0], e[1]);
+    return 0;
+  }
+};
+
+// The pair queries' host side (kano_pair_policies, kano_pair_masks,
+// kano_pair_verdicts, kano_verdict_matrix; kano_pairwalk.hpp): the range check
+// of the pairs (i < ni, j < nj), the tables of a context with the pairs' device
+// copy, and the launch shape -- the form from the mean list a pair walks (a
+// lane per pair makes that many dependent loads, a wave per pair ceil(s / 64)
+// rounds on 1/64 of the pairs in flight; form_knob 1 / 2 forces lane / wave)
+// and the grid (at most grid_knob blocks; 0: 8 per CU).
+int pairs_check(kano_ctx* ctx, const char* what, i64 Q, const int32_t* pairs, i64 ni, i64 nj);
+int pair_tables(kano_ctx* ctx, const char* what, const int32_t* pairs_dev, i64 Q, PairTables& t);
+void pair_shape(const kano_ctx* ctx, const PairTables& t, int form_knob, int grid_knob, i64 Q,
+                bool* wave, unsigned* grid);
 
 // matrix_diff's launches (kano_hip.hip, next to the kernels; the entry points
 // are kano_ext.hip's)

@@ -820,21 +820,11 @@ int kano_diff(kano_ctx* a, kano_ctx* b, int64_t* totals, int32_t* row_added,
   if (rl <= 0 || W <= 0) return 0;
   const bool full = row_added || row_removed || col_added || col_removed;
   // timing=1: the call's device time (the fill and the kernel, no copy)
-  hipEvent_t tev[2] = {nullptr, nullptr};
-  if (ctx->stage_timing) {
-    KCHK(hipEventCreate(&tev[0]));
-    KCHK(hipEventCreate(&tev[1]));
-    KCHK(hipEventRecord(tev[0], ctx->stream));
-  }
+  EventPair<> tev;
+  if (ctx->stage_timing) KTRY(tev.start(ctx));
   DiffBuf d{};
   KTRY(diff_pass(a, b, b->r0, rl, full, &d));
-  if (tev[0]) {
-    KCHK(hipEventRecord(tev[1], ctx->stream));
-    KCHK(hipEventSynchronize(tev[1]));
-    (void)hipEventElapsedTime(&ctx->diff_ms, tev[0], tev[1]);
-    (void)hipEventDestroy(tev[0]);
-    (void)hipEventDestroy(tev[1]);
-  }
+  KTRY(tev.stop(ctx, &ctx->diff_ms));
   u64 t[2] = {0, 0};
   KCHK(hipMemcpyAsync(t, d.totals, sizeof(t), hipMemcpyDeviceToHost, ctx->stream));
   if (row_added)
@@ -1023,12 +1013,8 @@ int kano_group_counts(kano_ctx* ctx, const int32_t* gsrc, int32_t Gs, const int3
     KCHK(hipMemcpyAsync(ip + b_gd + b_ord, runs.data(), b_run, hipMemcpyHostToDevice,
                         ctx->stream));
     // timing=1: the call's device time (the fills and the kernels, no copy)
-    hipEvent_t tev[2] = {nullptr, nullptr};
-    if (ctx->stage_timing) {
-      KCHK(hipEventCreate(&tev[0]));
-      KCHK(hipEventCreate(&tev[1]));
-      KCHK(hipEventRecord(tev[0], ctx->stream));
-    }
+    EventPair<> tev;
+    if (ctx->stage_timing) KTRY(tev.start(ctx));
     KCHK(hipMemsetAsync(out.p, 0, sizeof(u64) * cells, ctx->stream));
     if (row_counts) KCHK(hipMemsetAsync(rows.p, 0, sizeof(int32_t) * rcells, ctx->stream));
     const int32_t* gd_d = reinterpret_cast<const int32_t*>(ip);
@@ -1040,13 +1026,7 @@ int kano_group_counts(kano_ctx* ctx, const int32_t* gsrc, int32_t Gs, const int3
       KTRY(group_rows_launch(ctx, P_<u64>(masks), b0, k, ord_d, run_d, nruns, Gd, P_<u64>(out),
                              row_counts ? P_<int32_t>(rows) : nullptr));
     }
-    if (tev[0]) {
-      KCHK(hipEventRecord(tev[1], ctx->stream));
-      KCHK(hipEventSynchronize(tev[1]));
-      (void)hipEventElapsedTime(&ctx->group_ms, tev[0], tev[1]);
-      (void)hipEventDestroy(tev[0]);
-      (void)hipEventDestroy(tev[1]);
-    }
+    KTRY(tev.stop(ctx, &ctx->group_ms));
     KCHK(hipMemcpyAsync(counts, out.p, sizeof(u64) * cells, hipMemcpyDeviceToHost, ctx->stream));
     if (row_counts)
       KCHK(hipMemcpyAsync(row_counts, rows.p, sizeof(int32_t) * rcells, hipMemcpyDeviceToHost,
@@ -1089,7 +1069,7 @@ struct HopsStats {
 struct HopsBufs {
   DBuf dist, list, bits, small, items, gath, nodes;
   int32_t* pin = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  EventPair<> ev;   // timing=1: a batch's bracket
   i64 B = 0;
   float ms = 0.f;
 };
@@ -1099,10 +1079,6 @@ void hops_free(kano_ctx* ctx, HopsBufs& h, int rc) {
   for (DBuf* b : {&h.dist, &h.list, &h.bits, &h.small, &h.items, &h.gath, &h.nodes}) dfree(*b);
   if (h.pin) (void)hipHostFree(h.pin);
   h.pin = nullptr;
-  for (hipEvent_t& e : h.ev) {
-    if (e) (void)hipEventDestroy(e);
-    e = nullptr;
-  }
 }
 
 // the shared preamble: arguments, the matrix present and complete, every row held
@@ -1127,10 +1103,8 @@ int hops_alloc(kano_ctx* ctx, HopsBufs& h, i64 nsrc, bool targets) {
   KTRY(dalloc(ctx, h.small, sizeof(int32_t) * (size_t)(5 * h.B)));
   KCHK(hipHostMalloc(reinterpret_cast<void**>(&h.pin), sizeof(int32_t) * (size_t)(3 * h.B),
                      hipHostMallocDefault));
-  if (ctx->stage_timing) {
-    KCHK(hipEventCreate(&h.ev[0]));
-    KCHK(hipEventCreate(&h.ev[1]));
-  }
+  if (ctx->stage_timing)
+    for (hipEvent_t& e : h.ev.e) KCHK(hipEventCreate(&e));
   return 0;
 }
 
@@ -1211,11 +1185,8 @@ int hops_batch(kano_ctx* ctx, HopsBufs& h, i64 B, const int32_t* src, int32_t ma
 
 // closes the batch's timing (after the caller's gather / witness kernels)
 int hops_batch_end(kano_ctx* ctx, HopsBufs& h) {
-  if (!h.ev[0]) return 0;
-  KCHK(hipEventRecord(h.ev[1], ctx->stream));
-  KCHK(hipEventSynchronize(h.ev[1]));
   float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, h.ev[0], h.ev[1]);
+  KTRY(h.ev.stop(ctx, &ms));
   h.ms += ms;
   return 0;
 }
@@ -1549,12 +1520,8 @@ int kano_intents(kano_ctx* ctx, int64_t K, const uint64_t* src, const uint64_t* 
     KCHK(hipMemcpyAsync(dd.p, descs.data(), sizeof(IntentDesc) * descs.size(),
                         hipMemcpyHostToDevice, ctx->stream));
     // timing=1: the call's device time (the kernels, no copy)
-    hipEvent_t tev[2] = {nullptr, nullptr};
-    if (ctx->stage_timing) {
-      KCHK(hipEventCreate(&tev[0]));
-      KCHK(hipEventCreate(&tev[1]));
-      KCHK(hipEventRecord(tev[0], ctx->stream));
-    }
+    EventPair<> tev;
+    if (ctx->stage_timing) KTRY(tev.start(ctx));
     for (i64 p = 0; p < npass; ++p) {
       const i64 k0 = pass[p], Kp = pass[p + 1] - k0;
       const IntentDesc* de = P_<IntentDesc>(dd) + dbase[p];
@@ -1570,13 +1537,7 @@ int kano_intents(kano_ctx* ctx, int64_t K, const uint64_t* src, const uint64_t* 
                          nitems, (const int32_t*)P_<int32_t>(list), rp);
       KLAUNCH();
     }
-    if (tev[0]) {
-      KCHK(hipEventRecord(tev[1], ctx->stream));
-      KCHK(hipEventSynchronize(tev[1]));
-      (void)hipEventElapsedTime(&ctx->intents_ms, tev[0], tev[1]);
-      (void)hipEventDestroy(tev[0]);
-      (void)hipEventDestroy(tev[1]);
-    }
+    KTRY(tev.stop(ctx, &ctx->intents_ms));
     KCHK(hipMemcpyAsync(hres.data(), res.p, sizeof(u64) * hres.size(), hipMemcpyDeviceToHost,
                         ctx->stream));
     return sync(ctx);
@@ -1685,253 +1646,80 @@ int kano_intents_time(kano_ctx* ctx, float* ms) {
 }  // extern "C"
 
 // ===========================================================================
-// port_matrix / pair_ports: a subset of the policies' matrix and the pairs'
-// port masks from the resident tables (k_ports_*, k_pmask_*, kano_ports.hpp;
-// the class rows' expansion is kano_path's, path_expand_rows).  The matrix of
-// the source is not read and nothing of the source is written.
+// The derived matrices (port_matrix's kano_policy_subset, kano_verdict_matrix):
+// the held rows of dst written from src's resident tables.  The matrix of the
+// source is not read and nothing of the source is written.  Class-level rows
+// first (k_ports_class / k_verdict_class), expanded to the member rows by
+// kano_path's last step (path_expand_rows), then the added policies' rows.
 // ===========================================================================
 namespace {
-
-// the two events of a timing=1 call, destroyed also where the call fails
-// between their creation and its end
-struct EventPair {
-  hipEvent_t e[2] = {nullptr, nullptr};
-  hipEvent_t& operator[](int k) { return e[k]; }
-  ~EventPair() {
-    for (hipEvent_t x : e)
-      if (x) (void)hipEventDestroy(x);
-  }
-};
 
 const char* const NO_POLICIES =
     ": the matrix has no policies (an empty, copied, loaded, path or edge matrix holds rows only)";
 
-}  // namespace
+struct Geometry {
+  i64 P, A;                 // the source's build and added policies
+  i64 n, W, ldM, r0, rl;    // the destination's rows (the source's, checked)
+  i64 U, Ua, ldC;           // the source's row and column classes
+  bool classes;             // the build's part exists
+};
 
-extern "C" {
-
-int kano_policy_subset(kano_ctx* src, kano_ctx* dst, int64_t nids, const uint8_t* keep,
-                       int64_t* info) {
+// The arguments checked (missing: what of the call's own arrays is NULL, or
+// null), both contexts ready, the source's classes complete; g filled.
+int derived_begin(kano_ctx* src, kano_ctx* dst, const char* what, i64 nids, const char* missing,
+                  Geometry& g) {
   if (!src || !dst) return -EINVAL;
-  if (src == dst)
-    return fail(dst, -EINVAL, "kano_policy_subset: the destination must be another context");
-  if (src->device != dst->device)
-    return fail(dst, -EINVAL, "kano_policy_subset: contexts on two devices");
+  const std::string w(what);
+  if (src == dst) return fail(dst, -EINVAL, w + ": the destination must be another context");
+  if (src->device != dst->device) return fail(dst, -EINVAL, w + ": contexts on two devices");
   kano_ctx* ctx = dst;
   KCHK(hipSetDevice(dst->device));
-  {
-    const int rc = ensure_built(src);
-    if (rc) return fail(dst, rc, "kano_policy_subset: source: " + src->err);
-  }
+  int rc = ensure_built(src);
+  if (rc) return fail(dst, rc, w + ": source: " + src->err);
   if (src->lists_mode)
-    return fail(dst, -EINVAL, "kano_policy_subset: the source holds policy lists, not a matrix");
-  const i64 P = src->P, A = src->inc_A;
-  if (P == 0 && A == 0) return fail(dst, -EINVAL, std::string("kano_policy_subset") + NO_POLICIES);
-  if (nids != P + A)
-    return fail(dst, -EINVAL, "kano_policy_subset: nids = " + std::to_string(nids) + ", the source has " +
-                                  std::to_string(P + A) + " engine ids");
-  if (!keep) return fail(dst, -EINVAL, "kano_policy_subset: keep is NULL");
+    return fail(dst, -EINVAL, w + ": the source holds policy lists, not a matrix");
+  g.P = src->P;
+  g.A = src->inc_A;
+  if (g.P == 0 && g.A == 0) return fail(dst, -EINVAL, w + NO_POLICIES);
+  if (nids != g.P + g.A)
+    return fail(dst, -EINVAL, w + ": nids = " + std::to_string(nids) + ", the source has " +
+                                  std::to_string(g.P + g.A) + " engine ids");
+  if (missing) return fail(dst, -EINVAL, w + ": " + missing);
   KTRY(ensure_matrix(dst));
   if (dst->n != src->n || dst->r0 != src->r0 || dst->r1 != src->r1 || dst->ldM != src->ldM)
-    return fail(dst, -EINVAL, "kano_policy_subset: the destination must hold the same rows of a "
-                              "matrix of the same size");
-  {
-    const int rc = sync(src);   // the source's classes are complete
-    if (rc) return fail(dst, rc, "kano_policy_subset: source: " + src->err);
-  }
-  // use[p]: alive and kept
-  std::vector<uint8_t> use((size_t)nids);
-  i64 kept_build = 0, kept_added = 0;
-  for (i64 p = 0; p < nids; ++p) {
-    use[p] = keep[p] && !src->dead[p];
-    (p < P ? kept_build : kept_added) += use[p];
-  }
-  const i64 n = dst->n, W = dst->W, ldM = dst->ldM, r0 = dst->r0, rl = rows_local(dst);
-  const i64 U = src->rc.U, Ua = src->cc.U, ldC = src->ldC;
-  const bool classes = P > 0 && U > 0 && Ua > 0;
-  if (classes && (U + 15) / 16 > 65535)
-    return fail(dst, -ENOTSUP, "kano_policy_subset: more than 1,048,560 row classes");
-  src->subset_ms = dst->subset_ms = 0.f;
-  unsigned kept_classes = 0;
-  DBuf used, mcs, rt16, cnt;
-  auto run = [&]() -> int {
-    KTRY(dalloc(ctx, used, (size_t)nids));
-    KTRY(dalloc(ctx, cnt, sizeof(unsigned)));
-    KCHK(hipMemcpyAsync(used.p, use.data(), (size_t)nids, hipMemcpyHostToDevice, ctx->stream));
-    if (classes) {
-      KTRY(dalloc(ctx, mcs, sizeof(u64) * (size_t)(U * ldC)));
-      KTRY(dalloc(ctx, rt16, sizeof(uint16_t) * (size_t)(((U + 15) / 16) * Ua)));
-    }
-    EventPair tev;
-    if (src->stage_timing || dst->stage_timing) {
-      KCHK(hipEventCreate(&tev[0]));
-      KCHK(hipEventCreate(&tev[1]));
-      KCHK(hipEventRecord(tev[0], ctx->stream));
-    }
-    KCHK(hipMemsetAsync(cnt.p, 0, sizeof(unsigned), ctx->stream));
-    const uint8_t* use_d = P_<uint8_t>(used);
-    if (classes) {
-      int wl = 1;
-      while (wl < TPB && wl < ldC) wl <<= 1;
-      const i64 cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
-      hipLaunchKernelGGL(k_ports_class, dim3((unsigned)std::min<i64>(U, cus * 8)), dim3(TPB), 0,
-                         ctx->stream, U, (const i64*)P_<i64>(src->soffc),
-                         (const int32_t*)P_<int32_t>(src->slist), use_d,
-                         (const u64*)P_<u64>(src->AC), ldC, wl, P_<u64>(mcs), P_<unsigned>(cnt));
-      KLAUNCH();
-      // the class rows to the member rows: every word of every held row
-      KTRY(path_expand_rows(ctx, src, P_<u64>(mcs), ldC, U, Ua, rt16.p));
-    }
-    // the added policies OR-ed in; without classes the rows start as zeros
-    if (!classes || kept_added > 0) {
-      hipLaunchKernelGGL(k_ports_rows, dim3(nblk(rl * (ldM / 2))), dim3(TPB), 0, ctx->stream,
-                         classes ? 1 : 0, use_d, P, (const u64*)P_<u64>(src->asel),
-                         (const u64*)P_<u64>(src->aalw), W, kept_added > 0 ? A : 0, r0, rl, ldM,
-                         P_<u64>(dst->M));
-      KLAUNCH();
-    }
-    if (tev[0]) {
-      KCHK(hipEventRecord(tev[1], ctx->stream));
-      KCHK(hipEventSynchronize(tev[1]));
-      float ms = 0.f;
-      (void)hipEventElapsedTime(&ms, tev[0], tev[1]);
-      src->subset_ms = dst->subset_ms = ms;
-    }
-    KCHK(hipMemcpyAsync(&kept_classes, cnt.p, sizeof(unsigned), hipMemcpyDeviceToHost,
-                        ctx->stream));
-    return sync(ctx);
-  };
-  int rc = 0;
-  if (n > 0 && rl > 0) {
-    rc = run();
-    if (rc) (void)hipStreamSynchronize(ctx->stream);   // nothing in flight on the temporaries
-    for (DBuf* b : {&used, &mcs, &rt16, &cnt}) dfree(*b);
-    dst->cols_valid = false;
-    dst->rows_dirty = true;
-    dst->user_edited = true;
-  }
-  if (rc) return rc;
-  if (info) {
-    info[0] = kept_build;
-    info[1] = kept_added;
-    info[2] = (int64_t)kept_classes;
-  }
+    return fail(dst, -EINVAL,
+                w + ": the destination must hold the same rows of a matrix of the same size");
+  rc = sync(src);   // the source's classes are complete
+  if (rc) return fail(dst, rc, w + ": source: " + src->err);
+  g.n = dst->n, g.W = dst->W, g.ldM = dst->ldM, g.r0 = dst->r0, g.rl = rows_local(dst);
+  g.U = src->rc.U, g.Ua = src->cc.U, g.ldC = src->ldC;
+  g.classes = g.P > 0 && g.U > 0 && g.Ua > 0;
+  if (g.classes && (g.U + 15) / 16 > 65535)   // (path_expand_rows' grid)
+    return fail(dst, -ENOTSUP, w + ": more than 1,048,560 row classes");
   return 0;
 }
 
-int kano_pair_masks(kano_ctx* ctx, int64_t Q, const int32_t* pairs, int64_t nids, int32_t KW,
-                    const uint64_t* pmask, uint64_t* out) {
-  KTRY(ensure_built(ctx));
-  if (ctx->lists_mode)
-    return fail(ctx, -EINVAL, "kano_pair_masks: the context holds policy lists, not a matrix");
-  const i64 P = ctx->P, A = ctx->inc_A;
-  if (P == 0 && A == 0) return fail(ctx, -EINVAL, std::string("kano_pair_masks") + NO_POLICIES);
-  if (Q < 0 || KW <= 0) return fail(ctx, -EINVAL, "kano_pair_masks: Q < 0 or KW <= 0");
-  if (nids != P + A)
-    return fail(ctx, -EINVAL, "kano_pair_masks: nids = " + std::to_string(nids) + ", the context has " +
-                                  std::to_string(P + A) + " engine ids");
-  if (!pmask || (Q > 0 && (!pairs || !out)))
-    return fail(ctx, -EINVAL, "kano_pair_masks: pairs, pmask or out is NULL");
-  const i64 n = ctx->n;
-  for (i64 q = 0; q < Q; ++q)
-    if (pairs[2 * q] < 0 || pairs[2 * q] >= n || pairs[2 * q + 1] < 0 || pairs[2 * q + 1] >= n)
-      return fail(ctx, -ERANGE, "kano_pair_masks: pair " + std::to_string(q) + " out of range");
-  ctx->pmask_ms = 0.f;
-  if (Q == 0) return 0;
-  const size_t b_out = sizeof(u64) * (size_t)Q * (size_t)KW;
-  if (rows_local(ctx) <= 0) {
-    std::memset(out, 0, b_out);
-    return 0;
-  }
-  const bool any_dead = std::find(ctx->dead.begin(), ctx->dead.end(), 1) != ctx->dead.end();
-  DBuf pr, pm, dd, od;
-  auto run = [&]() -> int {
-    const size_t b_pm = sizeof(u64) * (size_t)nids * (size_t)KW;
-    KTRY(dalloc(ctx, pr, sizeof(int32_t) * 2 * (size_t)Q));
-    KTRY(dalloc(ctx, pm, b_pm));
-    KTRY(dalloc(ctx, od, b_out));
-    if (any_dead) KTRY(dalloc(ctx, dd, (size_t)nids));
-    KCHK(hipMemcpyAsync(pr.p, pairs, sizeof(int32_t) * 2 * (size_t)Q, hipMemcpyHostToDevice,
-                        ctx->stream));
-    KCHK(hipMemcpyAsync(pm.p, pmask, b_pm, hipMemcpyHostToDevice, ctx->stream));
-    if (any_dead)
-      KCHK(hipMemcpyAsync(dd.p, ctx->dead.data(), (size_t)nids, hipMemcpyHostToDevice,
-                          ctx->stream));
-    PairMaskArgs a{};
-    a.pairs = P_<int32_t>(pr);
-    a.Q = Q;
-    // (a build without policies has no classes: only the added part remains)
-    a.rcls = P > 0 && ctx->rc.U > 0 ? P_<int32_t>(ctx->rc.cls) : nullptr;
-    a.ccls = P_<int32_t>(ctx->cc.cls);
-    a.soffc = P_<i64>(ctx->soffc);
-    a.slist = P_<int32_t>(ctx->slist);
-    a.dead = any_dead ? P_<uint8_t>(dd) : nullptr;
-    a.AC = P_<u64>(ctx->AC);
-    a.ldC = ctx->ldC;
-    a.P = P;
-    a.asel = P_<u64>(ctx->asel);
-    a.aalw = P_<u64>(ctx->aalw);
-    a.W = ctx->W;
-    a.A = A;
-    a.r0 = ctx->r0;
-    a.r1 = ctx->r1;
-    a.pmask = P_<u64>(pm);
-    a.KW = KW;
-    a.out = P_<u64>(od);
-    if (a.rcls && !a.ccls) return fail(ctx, -EINVAL, "kano_pair_masks: no column classes");
-    // the form as kano_pair_policies picks it: by the mean list a pair walks
-    const i64 U = ctx->rc.U;
-    const i64 sbar = (a.rcls ? (ctx->nnz_sel + U - 1) / U : 0) + A;
-    bool wave = sbar > PMASK_WAVE_MIN;
-    if (ctx->pmask_form) wave = ctx->pmask_form == 2;
-    const i64 cap = ctx->pmask_grid > 0 ? ctx->pmask_grid : (i64)std::max(1, ctx->num_cus) * 8;
-    const unsigned grid =
-        (unsigned)std::min<i64>(cap, wave ? (Q + TPB / 64 - 1) / (TPB / 64) : nblk(Q));
-    EventPair tev;
-    if (ctx->stage_timing) {
-      KCHK(hipEventCreate(&tev[0]));
-      KCHK(hipEventCreate(&tev[1]));
-      KCHK(hipEventRecord(tev[0], ctx->stream));
-    }
-    if (wave) hipLaunchKernelGGL(k_pmask_wave, dim3(grid), dim3(TPB), 0, ctx->stream, a);
-    else hipLaunchKernelGGL(k_pmask_lane, dim3(grid), dim3(TPB), 0, ctx->stream, a);
-    KLAUNCH();
-    if (tev[0]) {
-      KCHK(hipEventRecord(tev[1], ctx->stream));
-      KCHK(hipEventSynchronize(tev[1]));
-      (void)hipEventElapsedTime(&ctx->pmask_ms, tev[0], tev[1]);
-    }
-    KCHK(hipMemcpyAsync(out, od.p, b_out, hipMemcpyDeviceToHost, ctx->stream));
-    return sync(ctx);
-  };
-  const int rc = run();
-  if (rc) (void)hipStreamSynchronize(ctx->stream);   // nothing in flight on the temporaries
-  for (DBuf* b : {&pr, &pm, &dd, &od}) dfree(*b);
-  return rc;
+// the class kernels' shape: wl lanes a class row (the smallest power of two
+// covering ldC, at most TPB) and at most cap blocks (8 per CU)
+void derived_shape(const kano_ctx* ctx, i64 ldC, int* wl, i64* cap) {
+  *wl = 1;
+  while (*wl < TPB && *wl < ldC) *wl <<= 1;
+  *cap = (ctx->num_cus > 0 ? ctx->num_cus : 256) * (i64)8;
 }
 
-int kano_policy_subset_time(kano_ctx* ctx, float* ms) {
-  if (!ctx || !ms) return -EINVAL;
-  *ms = ctx->subset_ms;
-  return 0;
+// a call's temporaries freed (after a failure: once nothing is in flight on them)
+void free_temps(kano_ctx* ctx, int rc, std::initializer_list<DBuf*> bufs) {
+  if (rc) (void)hipStreamSynchronize(ctx->stream);
+  for (DBuf* b : bufs) dfree(*b);
 }
 
-int kano_pair_masks_time(kano_ctx* ctx, float* ms) {
-  if (!ctx || !ms) return -EINVAL;
-  *ms = ctx->pmask_ms;
-  return 0;
+// the tail of a call that ran: dst's rows are new, its column results stale
+void derived_end(kano_ctx* dst, std::initializer_list<DBuf*> bufs, int rc) {
+  free_temps(dst, rc, bufs);
+  dst->cols_valid = false;
+  dst->rows_dirty = true;
+  dst->user_edited = true;
 }
-
-}  // extern "C"
-
-// ===========================================================================
-// verdict_matrix / pair_verdicts: deny rules and priorities over the resident
-// tables (k_verdict_*, kano_verdict.hpp; the class rows' expansion is
-// kano_path's, path_expand_rows; the rows of the added policies are marked by
-// k_inc_mark).  The matrix of the source is not read and nothing of the source
-// is written.
-// ===========================================================================
-namespace {
 
 // The keys of the engine ids (kano_verdict.hpp: rank * 2 + action, VD_DEAD
 // for a removed id) from the raw priorities: the rank is the position among
@@ -1965,35 +1753,153 @@ int verdict_keys(kano_ctx* src, kano_ctx* ctx, const char* what, i64 nids, const
 
 extern "C" {
 
+// port_matrix: the matrix of a subset of the policies (k_ports_*, kano_ports.hpp)
+int kano_policy_subset(kano_ctx* src, kano_ctx* dst, int64_t nids, const uint8_t* keep,
+                       int64_t* info) {
+  Geometry g;
+  KTRY(derived_begin(src, dst, "kano_policy_subset", nids, keep ? nullptr : "keep is NULL", g));
+  kano_ctx* ctx = dst;
+  // use[p]: alive and kept
+  std::vector<uint8_t> use((size_t)nids);
+  i64 kept_build = 0, kept_added = 0;
+  for (i64 p = 0; p < nids; ++p) {
+    use[p] = keep[p] && !src->dead[p];
+    (p < g.P ? kept_build : kept_added) += use[p];
+  }
+  src->subset_ms = dst->subset_ms = 0.f;
+  unsigned kept_classes = 0;
+  DBuf used, mcs, rt16, cnt;
+  auto run = [&]() -> int {
+    KTRY(dalloc(ctx, used, (size_t)nids));
+    KTRY(dalloc(ctx, cnt, sizeof(unsigned)));
+    KCHK(hipMemcpyAsync(used.p, use.data(), (size_t)nids, hipMemcpyHostToDevice, ctx->stream));
+    if (g.classes) {
+      KTRY(dalloc(ctx, mcs, sizeof(u64) * (size_t)(g.U * g.ldC)));
+      KTRY(dalloc(ctx, rt16, sizeof(uint16_t) * (size_t)(((g.U + 15) / 16) * g.Ua)));
+    }
+    EventPair<> tev;
+    if (src->stage_timing || dst->stage_timing) KTRY(tev.start(ctx));
+    KCHK(hipMemsetAsync(cnt.p, 0, sizeof(unsigned), ctx->stream));
+    const uint8_t* use_d = P_<uint8_t>(used);
+    if (g.classes) {
+      int wl;
+      i64 cap;
+      derived_shape(ctx, g.ldC, &wl, &cap);
+      hipLaunchKernelGGL(k_ports_class, dim3((unsigned)std::min<i64>(g.U, cap)), dim3(TPB), 0,
+                         ctx->stream, g.U, (const i64*)P_<i64>(src->soffc),
+                         (const int32_t*)P_<int32_t>(src->slist), use_d,
+                         (const u64*)P_<u64>(src->AC), g.ldC, wl, P_<u64>(mcs),
+                         P_<unsigned>(cnt));
+      KLAUNCH();
+      // the class rows to the member rows: every word of every held row
+      KTRY(path_expand_rows(ctx, src, P_<u64>(mcs), g.ldC, g.U, g.Ua, rt16.p));
+    }
+    // the added policies OR-ed in; without classes the rows start as zeros
+    if (!g.classes || kept_added > 0) {
+      hipLaunchKernelGGL(k_ports_rows, dim3(nblk(g.rl * (g.ldM / 2))), dim3(TPB), 0, ctx->stream,
+                         g.classes ? 1 : 0, use_d, g.P, (const u64*)P_<u64>(src->asel),
+                         (const u64*)P_<u64>(src->aalw), g.W, kept_added > 0 ? g.A : 0, g.r0,
+                         g.rl, g.ldM, P_<u64>(dst->M));
+      KLAUNCH();
+    }
+    KTRY(tev.stop(ctx, &dst->subset_ms));
+    src->subset_ms = dst->subset_ms;
+    KCHK(hipMemcpyAsync(&kept_classes, cnt.p, sizeof(unsigned), hipMemcpyDeviceToHost,
+                        ctx->stream));
+    return sync(ctx);
+  };
+  if (g.n > 0 && g.rl > 0) {
+    const int rc = run();
+    derived_end(dst, {&used, &mcs, &rt16, &cnt}, rc);
+    if (rc) return rc;
+  }
+  if (info) {
+    info[0] = kept_build;
+    info[1] = kept_added;
+    info[2] = (int64_t)kept_classes;
+  }
+  return 0;
+}
+
+// pair_ports: the pairs' port masks (k_pmask_*, kano_ports.hpp)
+int kano_pair_masks(kano_ctx* ctx, int64_t Q, const int32_t* pairs, int64_t nids, int32_t KW,
+                    const uint64_t* pmask, uint64_t* out) {
+  KTRY(ensure_built(ctx));
+  if (ctx->lists_mode)
+    return fail(ctx, -EINVAL, "kano_pair_masks: the context holds policy lists, not a matrix");
+  const i64 P = ctx->P, A = ctx->inc_A;
+  if (P == 0 && A == 0) return fail(ctx, -EINVAL, std::string("kano_pair_masks") + NO_POLICIES);
+  if (Q < 0 || KW <= 0) return fail(ctx, -EINVAL, "kano_pair_masks: Q < 0 or KW <= 0");
+  if (nids != P + A)
+    return fail(ctx, -EINVAL, "kano_pair_masks: nids = " + std::to_string(nids) + ", the context has " +
+                                  std::to_string(P + A) + " engine ids");
+  if (!pmask || (Q > 0 && (!pairs || !out)))
+    return fail(ctx, -EINVAL, "kano_pair_masks: pairs, pmask or out is NULL");
+  KTRY(pairs_check(ctx, "kano_pair_masks", Q, pairs, ctx->n, ctx->n));
+  ctx->pmask_ms = 0.f;
+  if (Q == 0) return 0;
+  const size_t b_out = sizeof(u64) * (size_t)Q * (size_t)KW;
+  if (rows_local(ctx) <= 0) {
+    std::memset(out, 0, b_out);
+    return 0;
+  }
+  const bool any_dead = std::find(ctx->dead.begin(), ctx->dead.end(), 1) != ctx->dead.end();
+  DBuf pr, pm, dd, od;
+  auto run = [&]() -> int {
+    const size_t b_pm = sizeof(u64) * (size_t)nids * (size_t)KW;
+    KTRY(dalloc(ctx, pr, sizeof(int32_t) * 2 * (size_t)Q));
+    KTRY(dalloc(ctx, pm, b_pm));
+    KTRY(dalloc(ctx, od, b_out));
+    if (any_dead) KTRY(dalloc(ctx, dd, (size_t)nids));
+    KCHK(hipMemcpyAsync(pr.p, pairs, sizeof(int32_t) * 2 * (size_t)Q, hipMemcpyHostToDevice,
+                        ctx->stream));
+    KCHK(hipMemcpyAsync(pm.p, pmask, b_pm, hipMemcpyHostToDevice, ctx->stream));
+    if (any_dead)
+      KCHK(hipMemcpyAsync(dd.p, ctx->dead.data(), (size_t)nids, hipMemcpyHostToDevice,
+                          ctx->stream));
+    PairMaskArgs a{};
+    KTRY(pair_tables(ctx, "kano_pair_masks", P_<int32_t>(pr), Q, a.t));
+    a.t.dead = any_dead ? P_<uint8_t>(dd) : nullptr;
+    a.pmask = P_<u64>(pm);
+    a.KW = KW;
+    a.out = P_<u64>(od);
+    bool wave;
+    unsigned grid;
+    pair_shape(ctx, a.t, ctx->pmask_form, ctx->pmask_grid, Q, &wave, &grid);
+    EventPair<> tev;
+    if (ctx->stage_timing) KTRY(tev.start(ctx));
+    if (wave) hipLaunchKernelGGL(k_pmask_wave, dim3(grid), dim3(TPB), 0, ctx->stream, a);
+    else hipLaunchKernelGGL(k_pmask_lane, dim3(grid), dim3(TPB), 0, ctx->stream, a);
+    KLAUNCH();
+    KTRY(tev.stop(ctx, &ctx->pmask_ms));
+    KCHK(hipMemcpyAsync(out, od.p, b_out, hipMemcpyDeviceToHost, ctx->stream));
+    return sync(ctx);
+  };
+  const int rc = run();
+  free_temps(ctx, rc, {&pr, &pm, &dd, &od});
+  return rc;
+}
+
+int kano_policy_subset_time(kano_ctx* ctx, float* ms) {
+  if (!ctx || !ms) return -EINVAL;
+  *ms = ctx->subset_ms;
+  return 0;
+}
+
+int kano_pair_masks_time(kano_ctx* ctx, float* ms) {
+  if (!ctx || !ms) return -EINVAL;
+  *ms = ctx->pmask_ms;
+  return 0;
+}
+
+// verdict_matrix: deny rules and priorities (k_verdict_*, kano_verdict.hpp;
+// the rows of the added policies are marked by k_inc_mark)
 int kano_verdict_matrix(kano_ctx* src, kano_ctx* dst, int64_t nids, const int32_t* prio,
                         const uint8_t* action, int64_t* info) {
-  if (!src || !dst) return -EINVAL;
-  if (src == dst)
-    return fail(dst, -EINVAL, "kano_verdict_matrix: the destination must be another context");
-  if (src->device != dst->device)
-    return fail(dst, -EINVAL, "kano_verdict_matrix: contexts on two devices");
+  Geometry g;
+  KTRY(derived_begin(src, dst, "kano_verdict_matrix", nids,
+                     prio && action ? nullptr : "prio or action is NULL", g));
   kano_ctx* ctx = dst;
-  KCHK(hipSetDevice(dst->device));
-  {
-    const int rc = ensure_built(src);
-    if (rc) return fail(dst, rc, "kano_verdict_matrix: source: " + src->err);
-  }
-  if (src->lists_mode)
-    return fail(dst, -EINVAL, "kano_verdict_matrix: the source holds policy lists, not a matrix");
-  const i64 P = src->P, A = src->inc_A;
-  if (P == 0 && A == 0) return fail(dst, -EINVAL, std::string("kano_verdict_matrix") + NO_POLICIES);
-  if (nids != P + A)
-    return fail(dst, -EINVAL, "kano_verdict_matrix: nids = " + std::to_string(nids) +
-                                  ", the source has " + std::to_string(P + A) + " engine ids");
-  if (!prio || !action) return fail(dst, -EINVAL, "kano_verdict_matrix: prio or action is NULL");
-  KTRY(ensure_matrix(dst));
-  if (dst->n != src->n || dst->r0 != src->r0 || dst->r1 != src->r1 || dst->ldM != src->ldM)
-    return fail(dst, -EINVAL, "kano_verdict_matrix: the destination must hold the same rows of a "
-                              "matrix of the same size");
-  {
-    const int rc = sync(src);   // the source's classes are complete
-    if (rc) return fail(dst, rc, "kano_verdict_matrix: source: " + src->err);
-  }
   std::vector<uint32_t> key;
   std::vector<int32_t> levels;
   i64 tally[2];
@@ -2001,12 +1907,7 @@ int kano_verdict_matrix(kano_ctx* src, kano_ctx* dst, int64_t nids, const int32_
   // aflag[P + t]: added policy t is alive (k_inc_mark's flags; the build's stay 0)
   std::vector<uint8_t> aflag((size_t)nids, 0);
   i64 alive_added = 0;
-  for (i64 t = 0; t < A; ++t) alive_added += aflag[P + t] = !src->dead[P + t];
-  const i64 n = dst->n, W = dst->W, ldM = dst->ldM, r0 = dst->r0, rl = rows_local(dst);
-  const i64 U = src->rc.U, Ua = src->cc.U, ldC = src->ldC;
-  const bool classes = P > 0 && U > 0 && Ua > 0;
-  if (classes && (U + 15) / 16 > 65535)
-    return fail(dst, -ENOTSUP, "kano_verdict_matrix: more than 1,048,560 row classes");
+  for (i64 t = 0; t < g.A; ++t) alive_added += aflag[g.P + t] = !src->dead[g.P + t];
   src->verdict_ms = dst->verdict_ms = 0.f;
   unsigned deny_classes = 0;
   DBuf keyd, flagd, cnt, pk, olist, okey, ocnt, vc, rt16, mrows;
@@ -2015,105 +1916,81 @@ int kano_verdict_matrix(kano_ctx* src, kano_ctx* dst, int64_t nids, const int32_
     KTRY(dalloc(ctx, cnt, 2 * sizeof(u64)));   // [0]: the marked rows, [1]: the deny classes
     KCHK(hipMemcpyAsync(keyd.p, key.data(), sizeof(uint32_t) * (size_t)nids, hipMemcpyHostToDevice,
                         ctx->stream));
-    if (classes) {
+    if (g.classes) {
       const size_t nnz = (size_t)std::max<i64>(1, src->nnz_sel);
       KTRY(dalloc(ctx, pk, sizeof(u64) * nnz));
       KTRY(dalloc(ctx, olist, sizeof(int32_t) * nnz));
       KTRY(dalloc(ctx, okey, sizeof(uint32_t) * nnz));
-      KTRY(dalloc(ctx, ocnt, sizeof(int32_t) * (size_t)U));
-      KTRY(dalloc(ctx, vc, sizeof(u64) * (size_t)(U * ldC)));
-      KTRY(dalloc(ctx, rt16, sizeof(uint16_t) * (size_t)(((U + 15) / 16) * Ua)));
+      KTRY(dalloc(ctx, ocnt, sizeof(int32_t) * (size_t)g.U));
+      KTRY(dalloc(ctx, vc, sizeof(u64) * (size_t)(g.U * g.ldC)));
+      KTRY(dalloc(ctx, rt16, sizeof(uint16_t) * (size_t)(((g.U + 15) / 16) * g.Ua)));
     }
     if (alive_added > 0) {
       KTRY(dalloc(ctx, flagd, (size_t)nids));
-      KTRY(dalloc(ctx, mrows, sizeof(int32_t) * (size_t)rl));
+      KTRY(dalloc(ctx, mrows, sizeof(int32_t) * (size_t)g.rl));
       KCHK(hipMemcpyAsync(flagd.p, aflag.data(), (size_t)nids, hipMemcpyHostToDevice, ctx->stream));
     }
-    EventPair tev;
-    if (src->stage_timing || dst->stage_timing) {
-      KCHK(hipEventCreate(&tev[0]));
-      KCHK(hipEventCreate(&tev[1]));
-      KCHK(hipEventRecord(tev[0], ctx->stream));
-    }
+    EventPair<> tev;
+    if (src->stage_timing || dst->stage_timing) KTRY(tev.start(ctx));
     KCHK(hipMemsetAsync(cnt.p, 0, 2 * sizeof(u64), ctx->stream));
     const uint32_t* key_d = P_<uint32_t>(keyd);
-    if (classes) {
-      int wl = 1;
-      while (wl < TPB && wl < ldC) wl <<= 1;
-      const i64 cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
-      hipLaunchKernelGGL(k_verdict_order, dim3((unsigned)std::min<i64>(U, cus * 8)), dim3(TPB), 0,
-                         ctx->stream, U, (const i64*)P_<i64>(src->soffc),
+    if (g.classes) {
+      int wl;
+      i64 cap;
+      derived_shape(ctx, g.ldC, &wl, &cap);
+      hipLaunchKernelGGL(k_verdict_order, dim3((unsigned)std::min<i64>(g.U, cap)), dim3(TPB), 0,
+                         ctx->stream, g.U, (const i64*)P_<i64>(src->soffc),
                          (const int32_t*)P_<int32_t>(src->slist), key_d, P_<u64>(pk),
-                         P_<int32_t>(olist),
-                         P_<uint32_t>(okey), P_<int32_t>(ocnt),
+                         P_<int32_t>(olist), P_<uint32_t>(okey), P_<int32_t>(ocnt),
                          reinterpret_cast<unsigned*>(P_<u64>(cnt) + 1));
       KLAUNCH();
       const i64 cpb = TPB / wl;
-      hipLaunchKernelGGL(k_verdict_class, dim3((unsigned)std::min<i64>((U + cpb - 1) / cpb, cus * 8)),
-                         dim3(TPB), 0, ctx->stream, U, (const i64*)P_<i64>(src->soffc),
+      hipLaunchKernelGGL(k_verdict_class, dim3((unsigned)std::min<i64>((g.U + cpb - 1) / cpb, cap)),
+                         dim3(TPB), 0, ctx->stream, g.U, (const i64*)P_<i64>(src->soffc),
                          (const int32_t*)P_<int32_t>(olist), (const uint32_t*)P_<uint32_t>(okey),
-                         (const int32_t*)P_<int32_t>(ocnt), (const u64*)P_<u64>(src->AC), ldC, wl,
-                         P_<u64>(vc));
+                         (const int32_t*)P_<int32_t>(ocnt), (const u64*)P_<u64>(src->AC), g.ldC,
+                         wl, P_<u64>(vc));
       KLAUNCH();
       // the class rows to the member rows: every word of every held row
-      KTRY(path_expand_rows(ctx, src, P_<u64>(vc), ldC, U, Ua, rt16.p));
+      KTRY(path_expand_rows(ctx, src, P_<u64>(vc), g.ldC, g.U, g.Ua, rt16.p));
     } else {
       // a build without policies has no classes: the rows start as zeros
-      KCHK(hipMemsetAsync(dst->M.p, 0, sizeof(u64) * (size_t)(rl * ldM), ctx->stream));
+      KCHK(hipMemsetAsync(dst->M.p, 0, sizeof(u64) * (size_t)(g.rl * g.ldM), ctx->stream));
     }
     if (alive_added > 0) {
       // the rows an alive added policy selects, resolved bit by bit
-      hipLaunchKernelGGL(k_inc_mark, dim3(nblk(rl)), dim3(TPB), 0, ctx->stream,
+      hipLaunchKernelGGL(k_inc_mark, dim3(nblk(g.rl)), dim3(TPB), 0, ctx->stream,
                          (const int32_t*)nullptr, (const i64*)nullptr, (const int32_t*)nullptr,
-                         (const uint8_t*)P_<uint8_t>(flagd), P, (const u64*)P_<u64>(src->asel), W,
-                         A, r0, rl, P_<int32_t>(mrows), P_<u64>(cnt));
+                         (const uint8_t*)P_<uint8_t>(flagd), g.P, (const u64*)P_<u64>(src->asel),
+                         g.W, g.A, g.r0, g.rl, P_<int32_t>(mrows), P_<u64>(cnt));
       KLAUNCH();
       u64 nrows = 0;
       KCHK(hipMemcpyAsync(&nrows, cnt.p, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
       KTRY(sync(ctx));
-      if (nrows > (u64)rl) return fail(ctx, -EIO, "kano_verdict_matrix: row count out of range");
+      if (nrows > (u64)g.rl)
+        return fail(ctx, -EIO, "kano_verdict_matrix: row count out of range");
       if (nrows > 0) {
         VerdictArgs a{};
-        a.rcls = classes ? P_<int32_t>(src->rc.cls) : nullptr;
-        a.ccls = P_<int32_t>(src->cc.cls);
-        a.soffc = P_<i64>(src->soffc);
-        a.slist = P_<int32_t>(src->slist);
-        a.key = key_d;
-        a.AC = P_<u64>(src->AC);
-        a.ldC = ldC;
-        a.P = P;
-        a.asel = P_<u64>(src->asel);
-        a.aalw = P_<u64>(src->aalw);
-        a.W = W;
-        a.A = A;
-        a.r0 = r0;
-        a.r1 = dst->r1;
+        const int rc = pair_tables(src, "kano_verdict_matrix", nullptr, 0, a.t);
+        if (rc) return fail(dst, rc, src->err);
+        if (!g.classes) a.t.rcls = nullptr;
+        a.t.key = key_d;
         hipLaunchKernelGGL(k_verdict_rows, dim3((unsigned)nrows), dim3(TPB), 0, ctx->stream, a,
-                           (const int32_t*)P_<int32_t>(mrows), n, P_<u64>(dst->M), ldM);
+                           (const int32_t*)P_<int32_t>(mrows), g.n, P_<u64>(dst->M), g.ldM);
         KLAUNCH();
       }
     }
-    if (tev[0]) {
-      KCHK(hipEventRecord(tev[1], ctx->stream));
-      KCHK(hipEventSynchronize(tev[1]));
-      float ms = 0.f;
-      (void)hipEventElapsedTime(&ms, tev[0], tev[1]);
-      src->verdict_ms = dst->verdict_ms = ms;
-    }
+    KTRY(tev.stop(ctx, &dst->verdict_ms));
+    src->verdict_ms = dst->verdict_ms;
     KCHK(hipMemcpyAsync(&deny_classes, P_<u64>(cnt) + 1, sizeof(unsigned), hipMemcpyDeviceToHost,
                         ctx->stream));
     return sync(ctx);
   };
-  int rc = 0;
-  if (n > 0 && rl > 0) {
-    rc = run();
-    if (rc) (void)hipStreamSynchronize(ctx->stream);   // nothing in flight on the temporaries
-    for (DBuf* b : {&keyd, &flagd, &cnt, &pk, &olist, &okey, &ocnt, &vc, &rt16, &mrows}) dfree(*b);
-    dst->cols_valid = false;
-    dst->rows_dirty = true;
-    dst->user_edited = true;
+  if (g.n > 0 && g.rl > 0) {
+    const int rc = run();
+    derived_end(dst, {&keyd, &flagd, &cnt, &pk, &olist, &okey, &ocnt, &vc, &rt16, &mrows}, rc);
+    if (rc) return rc;
   }
-  if (rc) return rc;
   if (info) {
     info[0] = tally[0];
     info[1] = tally[1];
@@ -2123,6 +2000,7 @@ int kano_verdict_matrix(kano_ctx* src, kano_ctx* dst, int64_t nids, const int32_
   return 0;
 }
 
+// pair_verdicts: the pairs' verdicts and deciders (k_verdict_lane / k_verdict_wave)
 int kano_pair_verdicts(kano_ctx* ctx, int64_t Q, const int32_t* pairs, int64_t nids,
                        const int32_t* prio, const uint8_t* action, uint8_t* verdict,
                        int32_t* decided_prio, int32_t* decider, int64_t* counts) {
@@ -2141,20 +2019,14 @@ int kano_pair_verdicts(kano_ctx* ctx, int64_t Q, const int32_t* pairs, int64_t n
   std::vector<int32_t> levels;
   i64 tally[2];
   KTRY(verdict_keys(ctx, ctx, "kano_pair_verdicts", nids, prio, action, key, levels, tally));
-  const i64 n = ctx->n;
-  for (i64 q = 0; q < Q; ++q)
-    if (pairs[2 * q] < 0 || pairs[2 * q] >= n || pairs[2 * q + 1] < 0 || pairs[2 * q + 1] >= n)
-      return fail(ctx, -ERANGE, "kano_pair_verdicts: pair " + std::to_string(q) + " out of range");
+  KTRY(pairs_check(ctx, "kano_pair_verdicts", Q, pairs, ctx->n, ctx->n));
   ctx->pverdict_ms = 0.f;
   if (counts) counts[0] = counts[1] = counts[2] = 0;
   if (Q == 0) return 0;
-  auto none = [&]() {
+  if (rows_local(ctx) <= 0) {
     std::memset(verdict, 0, (size_t)Q);
     if (decided_prio) std::memset(decided_prio, 0, sizeof(int32_t) * (size_t)Q);
     if (decider) std::fill(decider, decider + Q, -1);
-  };
-  if (rows_local(ctx) <= 0) {
-    none();
     return 0;
   }
   std::vector<uint32_t> hkey((size_t)Q);
@@ -2170,48 +2042,19 @@ int kano_pair_verdicts(kano_ctx* ctx, int64_t Q, const int32_t* pairs, int64_t n
     KCHK(hipMemcpyAsync(kd.p, key.data(), sizeof(uint32_t) * (size_t)nids, hipMemcpyHostToDevice,
                         ctx->stream));
     VerdictArgs a{};
-    a.pairs = P_<int32_t>(pr);
-    a.Q = Q;
-    // (a build without policies has no classes: only the added part remains)
-    a.rcls = P > 0 && ctx->rc.U > 0 ? P_<int32_t>(ctx->rc.cls) : nullptr;
-    a.ccls = P_<int32_t>(ctx->cc.cls);
-    a.soffc = P_<i64>(ctx->soffc);
-    a.slist = P_<int32_t>(ctx->slist);
-    a.key = P_<uint32_t>(kd);
-    a.AC = P_<u64>(ctx->AC);
-    a.ldC = ctx->ldC;
-    a.P = P;
-    a.asel = P_<u64>(ctx->asel);
-    a.aalw = P_<u64>(ctx->aalw);
-    a.W = ctx->W;
-    a.A = A;
-    a.r0 = ctx->r0;
-    a.r1 = ctx->r1;
+    KTRY(pair_tables(ctx, "kano_pair_verdicts", P_<int32_t>(pr), Q, a.t));
+    a.t.key = P_<uint32_t>(kd);
     a.out_key = P_<uint32_t>(ok);
     a.out_id = P_<int32_t>(oi);
-    if (a.rcls && !a.ccls) return fail(ctx, -EINVAL, "kano_pair_verdicts: no column classes");
-    // the form as kano_pair_masks picks it: by the mean list a pair walks
-    const i64 U = ctx->rc.U;
-    const i64 sbar = (a.rcls ? (ctx->nnz_sel + U - 1) / U : 0) + A;
-    bool wave = sbar > VERDICT_WAVE_MIN;
-    if (ctx->verdict_form) wave = ctx->verdict_form == 2;
-    const i64 cap = ctx->verdict_grid > 0 ? ctx->verdict_grid : (i64)std::max(1, ctx->num_cus) * 8;
-    const unsigned grid =
-        (unsigned)std::min<i64>(cap, wave ? (Q + TPB / 64 - 1) / (TPB / 64) : nblk(Q));
-    EventPair tev;
-    if (ctx->stage_timing) {
-      KCHK(hipEventCreate(&tev[0]));
-      KCHK(hipEventCreate(&tev[1]));
-      KCHK(hipEventRecord(tev[0], ctx->stream));
-    }
+    bool wave;
+    unsigned grid;
+    pair_shape(ctx, a.t, ctx->verdict_form, ctx->verdict_grid, Q, &wave, &grid);
+    EventPair<> tev;
+    if (ctx->stage_timing) KTRY(tev.start(ctx));
     if (wave) hipLaunchKernelGGL(k_verdict_wave, dim3(grid), dim3(TPB), 0, ctx->stream, a);
     else hipLaunchKernelGGL(k_verdict_lane, dim3(grid), dim3(TPB), 0, ctx->stream, a);
     KLAUNCH();
-    if (tev[0]) {
-      KCHK(hipEventRecord(tev[1], ctx->stream));
-      KCHK(hipEventSynchronize(tev[1]));
-      (void)hipEventElapsedTime(&ctx->pverdict_ms, tev[0], tev[1]);
-    }
+    KTRY(tev.stop(ctx, &ctx->pverdict_ms));
     KCHK(hipMemcpyAsync(hkey.data(), ok.p, sizeof(uint32_t) * (size_t)Q, hipMemcpyDeviceToHost,
                         ctx->stream));
     KCHK(hipMemcpyAsync(hid.data(), oi.p, sizeof(int32_t) * (size_t)Q, hipMemcpyDeviceToHost,
@@ -2219,8 +2062,7 @@ int kano_pair_verdicts(kano_ctx* ctx, int64_t Q, const int32_t* pairs, int64_t n
     return sync(ctx);
   };
   const int rc = run();
-  if (rc) (void)hipStreamSynchronize(ctx->stream);   // nothing in flight on the temporaries
-  for (DBuf* b : {&pr, &kd, &ok, &oi}) dfree(*b);
+  free_temps(ctx, rc, {&pr, &kd, &ok, &oi});
   if (rc) return rc;
   // the keys back to verdicts and raw priorities; a pair whose i this context
   // does not hold matched nothing and adds to no count

@@ -3770,12 +3770,8 @@ int impact_run(kano_ctx* ctx, int mode, int64_t* impact, uint8_t* essential,
   KTRY(dalloc(ctx, res, bytes));
   // timing=1: the call's device time (the fill and the kernel, no copy) for
   // kano_stage_times, slot 7
-  hipEvent_t tev[2] = {nullptr, nullptr};
-  if (ctx->stage_timing) {
-    KCHK(hipEventCreate(&tev[0]));
-    KCHK(hipEventCreate(&tev[1]));
-    KCHK(hipEventRecord(tev[0], ctx->stream));
-  }
+  EventPair<> tev;
+  if (ctx->stage_timing) KTRY(tev.start(ctx));
   if (P > 0) KCHK(hipMemsetAsync(res.p, 0, bytes, ctx->stream));
   if (P > 0 && U > 0 && UA > 0) {
     ImpactArgs a{};
@@ -3827,13 +3823,7 @@ int impact_run(kano_ctx* ctx, int mode, int64_t* impact, uint8_t* essential,
     }
     KLAUNCH();
   }
-  if (tev[0]) {
-    KCHK(hipEventRecord(tev[1], ctx->stream));
-    KCHK(hipEventSynchronize(tev[1]));
-    (void)hipEventElapsedTime(&ctx->impact_ms, tev[0], tev[1]);
-    (void)hipEventDestroy(tev[0]);
-    (void)hipEventDestroy(tev[1]);
-  }
+  KTRY(tev.stop(ctx, &ctx->impact_ms));
   i64 nred = 0;
   if (mode == 0) {
     if (P > 0)
@@ -3903,6 +3893,50 @@ int kano_policy_impact_lists(kano_ctx* ctx, int64_t n_lists, int64_t nbits, int6
 
 }  // extern "C"
 
+// the pair queries' host side (kano_engine.hpp)
+namespace kano_eng {
+
+int pairs_check(kano_ctx* ctx, const char* what, i64 Q, const int32_t* pairs, i64 ni, i64 nj) {
+  for (i64 q = 0; q < Q; ++q)
+    if (pairs[2 * q] < 0 || pairs[2 * q] >= ni || pairs[2 * q + 1] < 0 || pairs[2 * q + 1] >= nj)
+      return fail(ctx, -ERANGE, std::string(what) + ": pair " + std::to_string(q) + " out of range");
+  return 0;
+}
+
+int pair_tables(kano_ctx* ctx, const char* what, const int32_t* pairs_dev, i64 Q, PairTables& t) {
+  const bool lists = ctx->lists_mode;
+  t.pairs = pairs_dev;
+  t.Q = Q;
+  // (a build without policies has no classes: only the added part remains)
+  t.rcls = ctx->P > 0 && ctx->rc.U > 0 ? P_<int32_t>(ctx->rc.cls) : nullptr;
+  t.ccls = lists ? nullptr : P_<int32_t>(ctx->cc.cls);   // lists: every pod a class
+  t.soffc = P_<i64>(ctx->soffc);
+  t.slist = P_<int32_t>(ctx->slist);
+  t.AC = P_<u64>(ctx->AC);
+  t.ldC = ctx->ldC;
+  t.P = ctx->P;
+  t.asel = P_<u64>(ctx->asel);
+  t.aalw = P_<u64>(ctx->aalw);
+  t.W = ctx->W;
+  t.A = lists ? 0 : ctx->inc_A;
+  t.r0 = ctx->r0;
+  t.r1 = ctx->r1;
+  if (t.rcls && !lists && !t.ccls)
+    return fail(ctx, -EINVAL, std::string(what) + ": no column classes");
+  return 0;
+}
+
+void pair_shape(const kano_ctx* ctx, const PairTables& t, int form_knob, int grid_knob, i64 Q,
+                bool* wave, unsigned* grid) {
+  const i64 U = ctx->rc.U;
+  const i64 sbar = (t.rcls ? (ctx->nnz_sel + U - 1) / U : 0) + t.A;
+  *wave = form_knob ? form_knob == 2 : sbar > PAIR_WAVE_MIN;
+  const i64 cap = grid_knob > 0 ? grid_knob : (i64)std::max(1, ctx->num_cus) * 8;
+  *grid = (unsigned)std::min<i64>(cap, *wave ? (Q + WPB - 1) / WPB : nblk(Q));
+}
+
+}  // namespace kano_eng
+
 namespace {
 // pair_policies on the resident tables (k_pair_lane / k_pair_wave): the count
 // pass, in mode 0 the offsets' scan and the emit pass.  Only the pp_* buffers
@@ -3918,11 +3952,8 @@ int pair_run(kano_ctx* ctx, const char* what, i64 Q, const int32_t* pairs, int m
   if (total) *total = 0;
   if (Q < 0 || (Q > 0 && !pairs)) return fail(ctx, -EINVAL, w + ": bad arguments");
   const bool lists = ctx->lists_mode;
-  const i64 P = ctx->P, A = lists ? 0 : ctx->inc_A, PT = P + A;
-  const i64 ni = lists ? ctx->rc.U : ctx->n, nj = ctx->n;
-  for (i64 q = 0; q < Q; ++q)
-    if (pairs[2 * q] < 0 || pairs[2 * q] >= ni || pairs[2 * q + 1] < 0 || pairs[2 * q + 1] >= nj)
-      return fail(ctx, -ERANGE, w + ": pair " + std::to_string(q) + " out of range");
+  const i64 PT = ctx->P + (lists ? 0 : ctx->inc_A);
+  KTRY(pairs_check(ctx, what, Q, pairs, lists ? ctx->rc.U : ctx->n, ctx->n));
   if (hist && PT > 0) std::memset(hist, 0, sizeof(int64_t) * (size_t)PT);
   if (Q == 0) {
     if (mode == 0) {
@@ -3944,42 +3975,17 @@ int pair_run(kano_ctx* ctx, const char* what, i64 Q, const int32_t* pairs, int m
     KCHK(hipMemcpyAsync(ctx->pp_dead.p, ctx->dead.data(), (size_t)PT, hipMemcpyHostToDevice,
                         ctx->stream));
   PairArgs a{};
-  a.pairs = P_<int32_t>(ctx->pp_pairs);
-  a.Q = Q;
-  // (a build without policies has no classes: only the added part remains)
-  a.rcls = P > 0 && ctx->rc.U > 0 ? P_<int32_t>(ctx->rc.cls) : nullptr;
-  a.ccls = lists ? nullptr : P_<int32_t>(ctx->cc.cls);   // lists: every pod a class
-  a.soffc = P_<i64>(ctx->soffc);
-  a.slist = P_<int32_t>(ctx->slist);
-  a.dead = any_dead ? P_<uint8_t>(ctx->pp_dead) : nullptr;
-  a.AC = P_<u64>(ctx->AC);
-  a.ldC = ctx->ldC;
-  a.P = P;
-  a.asel = P_<u64>(ctx->asel);
-  a.aalw = P_<u64>(ctx->aalw);
-  a.W = ctx->W;
-  a.A = A;
-  a.r0 = ctx->r0;
-  a.r1 = ctx->r1;
+  KTRY(pair_tables(ctx, what, P_<int32_t>(ctx->pp_pairs), Q, a.t));
+  a.t.dead = any_dead ? P_<uint8_t>(ctx->pp_dead) : nullptr;
   a.cover = P_<int32_t>(ctx->pp_cover);
   a.hist = hist ? P_<i64>(ctx->pp_hist) : nullptr;
-  if (a.rcls && !lists && !a.ccls) return fail(ctx, -EINVAL, w + ": no column classes");
-  // The form, from the mean list a pair walks (s = policies per row class,
-  // plus the added ones): a lane per pair makes that many dependent loads, a
-  // wave per pair ceil(s / 64) rounds on 1/64 of the pairs in flight.
-  const i64 U = ctx->rc.U;
-  const i64 sbar = (a.rcls ? (ctx->nnz_sel + U - 1) / U : 0) + A;
-  bool wave = sbar > PAIR_WAVE_MIN;
-  if (ctx->pair_form) wave = ctx->pair_form == 2;
-  const i64 cap = ctx->pair_grid > 0 ? ctx->pair_grid : (i64)std::max(1, ctx->num_cus) * 8;
-  const unsigned grid = (unsigned)std::min<i64>(cap, wave ? (Q + WPB - 1) / WPB : nblk(Q));
+  bool wave;
+  unsigned grid;
+  pair_shape(ctx, a.t, ctx->pair_form, ctx->pair_grid, Q, &wave, &grid);
   // timing=1: the call's device time, [0, 1] the fill, the count pass and the
   // scan, [2, 3] the emit pass (the host reads the total in between)
-  hipEvent_t tev[4] = {nullptr, nullptr, nullptr, nullptr};
-  if (ctx->stage_timing) {
-    for (auto& e : tev) KCHK(hipEventCreate(&e));
-    KCHK(hipEventRecord(tev[0], ctx->stream));
-  }
+  EventPair<4> tev;
+  if (ctx->stage_timing) KTRY(tev.start(ctx));
   if (hist && PT > 0) KCHK(hipMemsetAsync(ctx->pp_hist.p, 0, sizeof(i64) * (size_t)PT, ctx->stream));
   // (direct launches, no kernel-pointer variable: tests/test_launch_ir.py)
   if (wave) hipLaunchKernelGGL((k_pair_wave<false>), dim3(grid), dim3(TPB), 0, ctx->stream, a);
@@ -4024,7 +4030,6 @@ int pair_run(kano_ctx* ctx, const char* what, i64 Q, const int32_t* pairs, int m
     (void)hipEventElapsedTime(&ms, tev[0], tev[1]);
     if (mode == 0) (void)hipEventElapsedTime(&ms2, tev[2], tev[3]);
     ctx->pair_ms = ms + ms2;
-    for (auto& e : tev) (void)hipEventDestroy(e);
   }
   if (mode == 0) {
     ctx->pair_total = tot;

@@ -9,6 +9,7 @@
 //   policy_shadow              algorithm.py:58-80
 //   policy_conflict (working)  algorithm.py:83-100 as intended: disjoint allow sets
 #pragma once
+#include "kano_pairwalk.hpp"
 #include "kano_prims.hpp"
 
 namespace kano {
@@ -3209,13 +3210,13 @@ __global__ __launch_bounds__(TPB) void k_impact_rows(ImpactArgs a) {
 // pair_policies: which policies allow a given pod pair.
 //   pols(i, j)  = ascending engine ids p with i in sel_p and j in allow_p
 //   cover(i, j) = |pols(i, j)|
-// over the matrix's current policies.  For a query pair (i, j) with row class
-// c = rcls[i] and column class x = ccls[j] (lists mode: ccls null, x = j) the
-// build's part is every alive p of S(c) whose bit x is set in AC[p]; the
-// added policies (ids P + q) are tested on their pod-level sets asel / aalw.
-// S(c) is ascending and the added ids follow the build's, so every pair's ids
-// come out ascending from a serial walk or a ballot prefix.  A pair whose i
-// lies outside [r0, r1) (another shard's row) has no policies here.
+// over the matrix's current policies: the alive policies of the pair walk
+// (kano_pairwalk.hpp: the tables, the two hit tests, the ownership rule), whose
+// ids come out ascending from a serial walk or a ballot prefix.  The ballots
+// (histogram merge, emit position) need every lane in every round, so the two
+// kernels keep their own loops; they also still spell the walk's tests out by
+// hand: rewritten over the helpers they computed the same but not in the same
+// time ("The pair walk").
 //
 // One walk, two passes: EMIT = false counts (cover[q], and hist[p] += 1 per
 // listed policy when hist is given), EMIT = true writes the ids at off[q]
@@ -3230,30 +3231,13 @@ __global__ __launch_bounds__(TPB) void k_impact_rows(ImpactArgs a) {
 // k_pair_lane is grid-stride over the pairs.
 // ===========================================================================
 struct PairArgs {
-  const int32_t* pairs;  // (i, j) x Q
-  i64 Q;
-  const int32_t* rcls;   // null: the build had no policies (only the added part)
-  const int32_t* ccls;   // null: x = j
-  const i64* soffc;
-  const int32_t* slist;
-  const uint8_t* dead;   // P + A flags; null: none removed
-  const u64* AC;
-  i64 ldC;
-  i64 P;
-  const u64* asel;
-  const u64* aalw;
-  i64 W, A;
-  i64 r0, r1;
+  PairTables t;          // (t.dead: the removed ids' flags)
   int32_t* cover;        // !EMIT
   i64* hist;             // !EMIT, nullable
   const i64* off;        // EMIT
   int32_t* pol;          // EMIT
   i64 cap;               // EMIT: entries of pol
 };
-
-// the wave form when a pair walks more than this many policies on average
-// (mean |S(c)| + added policies; the host's choice, kano_hip.hip pair_run)
-constexpr i64 PAIR_WAVE_MIN = 16;
 
 // hist[key] += 1 for every active lane, lanes with equal keys merged into one
 // 64-bit atomic (as wave_agg_inc).  Every lane of the wave must call it.
@@ -3279,29 +3263,29 @@ template <bool EMIT>
 __global__ __launch_bounds__(TPB) void k_pair_lane(PairArgs a) {
   const i64 stride = (i64)gridDim.x * TPB;
   // (whole waves leave together: the loop bound is the wave's first pair)
-  for (i64 q0 = (i64)blockIdx.x * TPB + (threadIdx.x & ~63); q0 < a.Q; q0 += stride) {
+  for (i64 q0 = (i64)blockIdx.x * TPB + (threadIdx.x & ~63); q0 < a.t.Q; q0 += stride) {
     const i64 q = q0 + (threadIdx.x & 63);
     i64 i = 0, j = 0, s0 = 0, s = 0, x = 0;
     bool own = false;
-    if (q < a.Q) {
-      i = a.pairs[2 * q];
-      j = a.pairs[2 * q + 1];
-      own = i >= a.r0 && i < a.r1;
-      if (own && a.rcls) {
-        const int32_t c = a.rcls[i];
-        s0 = a.soffc[c];
-        s = a.soffc[c + 1] - s0;
-        x = a.ccls ? a.ccls[j] : j;
+    if (q < a.t.Q) {
+      i = a.t.pairs[2 * q];
+      j = a.t.pairs[2 * q + 1];
+      own = i >= a.t.r0 && i < a.t.r1;
+      if (own && a.t.rcls) {
+        const int32_t c = a.t.rcls[i];
+        s0 = a.t.soffc[c];
+        s = a.t.soffc[c + 1] - s0;
+        x = a.t.ccls ? a.t.ccls[j] : j;
       }
     }
-    i64 o = EMIT && q < a.Q ? a.off[q] : 0;
+    i64 o = EMIT && q < a.t.Q ? a.off[q] : 0;
     int32_t cnt = 0;
     for (i64 k = 0; __ballot(k < s) != 0ull; ++k) {
       int32_t p = 0;
       bool hit = false;
       if (k < s) {
-        p = a.slist[s0 + k];
-        hit = !(a.dead && a.dead[p]) && ((a.AC[(i64)p * a.ldC + (x >> 6)] >> (x & 63)) & 1ull);
+        p = a.t.slist[s0 + k];
+        hit = !(a.t.dead && a.t.dead[p]) && ((a.t.AC[(i64)p * a.t.ldC + (x >> 6)] >> (x & 63)) & 1ull);
       }
       if (EMIT) {
         if (hit && o < a.cap) a.pol[o] = p;
@@ -3311,19 +3295,19 @@ __global__ __launch_bounds__(TPB) void k_pair_lane(PairArgs a) {
         if (a.hist) wave_agg_add64(a.hist, p, hit);
       }
     }
-    for (i64 t = 0; t < a.A; ++t) {
-      const bool hit = own && !(a.dead && a.dead[a.P + t]) &&
-                       ((a.asel[t * a.W + (i >> 6)] >> (i & 63)) & 1ull) &&
-                       ((a.aalw[t * a.W + (j >> 6)] >> (j & 63)) & 1ull);
+    for (i64 t = 0; t < a.t.A; ++t) {
+      const bool hit = own && !(a.t.dead && a.t.dead[a.t.P + t]) &&
+                       ((a.t.asel[t * a.t.W + (i >> 6)] >> (i & 63)) & 1ull) &&
+                       ((a.t.aalw[t * a.t.W + (j >> 6)] >> (j & 63)) & 1ull);
       if (EMIT) {
-        if (hit && o < a.cap) a.pol[o] = (int32_t)(a.P + t);
+        if (hit && o < a.cap) a.pol[o] = (int32_t)(a.t.P + t);
         o += hit;
       } else {
         cnt += hit;
-        if (a.hist) wave_agg_add64(a.hist, a.P + t, hit);
+        if (a.hist) wave_agg_add64(a.hist, a.t.P + t, hit);
       }
     }
-    if (!EMIT && q < a.Q) a.cover[q] = cnt;
+    if (!EMIT && q < a.t.Q) a.cover[q] = cnt;
   }
 }
 
@@ -3357,14 +3341,14 @@ __global__ __launch_bounds__(TPB) void k_pair_wave(PairArgs a) {
   const u64 below = (1ull << lane) - 1ull;
   // wave gw of nw takes pairs [gw * per, (gw + 1) * per)
   const i64 nw = (i64)gridDim.x * WPB, gw = (i64)blockIdx.x * WPB + (threadIdx.x >> 6);
-  const i64 per = (a.Q + nw - 1) / nw;
-  const i64 q1 = min(a.Q, (gw + 1) * per);
+  const i64 per = (a.t.Q + nw - 1) / nw;
+  const i64 q1 = min(a.t.Q, (gw + 1) * per);
   PairAcc acc[PAIR_ACC + 1];   // (the last one: the first 64 added policies)
 #pragma unroll
   for (int r = 0; r <= PAIR_ACC; ++r) acc[r] = PairAcc{0, 0};
   for (i64 q = gw * per; q < q1; ++q) {          // wave-uniform
-    const i64 i = a.pairs[2 * q], j = a.pairs[2 * q + 1];
-    const bool own = i >= a.r0 && i < a.r1;
+    const i64 i = a.t.pairs[2 * q], j = a.t.pairs[2 * q + 1];
+    const bool own = i >= a.t.r0 && i < a.t.r1;
     i64 o = EMIT ? a.off[q] : 0;
     int32_t cnt = 0;
     // one round: lanes k = b + lane of the list; ac: where the histogram sums
@@ -3373,8 +3357,8 @@ __global__ __launch_bounds__(TPB) void k_pair_wave(PairArgs a) {
       int32_t p = 0;
       bool hit = false;
       if (k < s) {
-        p = a.slist[s0 + k];
-        hit = !(a.dead && a.dead[p]) && ((a.AC[(i64)p * a.ldC + (x >> 6)] >> (x & 63)) & 1ull);
+        p = a.t.slist[s0 + k];
+        hit = !(a.t.dead && a.t.dead[p]) && ((a.t.AC[(i64)p * a.t.ldC + (x >> 6)] >> (x & 63)) & 1ull);
       }
       const u64 bal = __ballot(hit);
       if (EMIT) {
@@ -3389,31 +3373,31 @@ __global__ __launch_bounds__(TPB) void k_pair_wave(PairArgs a) {
         }
       }
     };
-    if (own && a.rcls) {
-      const int32_t c = a.rcls[i];
-      const i64 s0 = a.soffc[c], s = a.soffc[c + 1] - s0;
-      const i64 x = a.ccls ? a.ccls[j] : j;
+    if (own && a.t.rcls) {
+      const int32_t c = a.t.rcls[i];
+      const i64 s0 = a.t.soffc[c], s = a.t.soffc[c + 1] - s0;
+      const i64 x = a.t.ccls ? a.t.ccls[j] : j;
 #pragma unroll
       for (int r = 0; r < PAIR_ACC; ++r)
         if ((i64)r * 64 < s) round(s0, s, x, (i64)r * 64, &acc[r]);
       for (i64 b = (i64)PAIR_ACC * 64; b < s; b += 64) round(s0, s, x, b, nullptr);
     }
     if (own) {
-      for (i64 b = 0; b < a.A; b += 64) {
+      for (i64 b = 0; b < a.t.A; b += 64) {
         const i64 t = b + lane;
-        const bool hit = t < a.A && !(a.dead && a.dead[a.P + t]) &&
-                         ((a.asel[t * a.W + (i >> 6)] >> (i & 63)) & 1ull) &&
-                         ((a.aalw[t * a.W + (j >> 6)] >> (j & 63)) & 1ull);
+        const bool hit = t < a.t.A && !(a.t.dead && a.t.dead[a.t.P + t]) &&
+                         ((a.t.asel[t * a.t.W + (i >> 6)] >> (i & 63)) & 1ull) &&
+                         ((a.t.aalw[t * a.t.W + (j >> 6)] >> (j & 63)) & 1ull);
         const u64 bal = __ballot(hit);
         if (EMIT) {
           const i64 at = o + __popcll(bal & below);
-          if (hit && at < a.cap) a.pol[at] = (int32_t)(a.P + t);
+          if (hit && at < a.cap) a.pol[at] = (int32_t)(a.t.P + t);
           o += __popcll(bal);
         } else {
           cnt += __popcll(bal);
           if (hit && a.hist) {
-            if (b == 0) pair_acc_add(a.hist, acc[PAIR_ACC], (int32_t)(a.P + t));
-            else atomicAdd(reinterpret_cast<unsigned long long*>(&a.hist[a.P + t]), 1ull);
+            if (b == 0) pair_acc_add(a.hist, acc[PAIR_ACC], (int32_t)(a.t.P + t));
+            else atomicAdd(reinterpret_cast<unsigned long long*>(&a.hist[a.t.P + t]), 1ull);
           }
         }
       }

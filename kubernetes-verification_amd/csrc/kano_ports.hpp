@@ -13,6 +13,7 @@
 //   k_ports_rows     only with kept added policies (or without classes): their
 //                    pod-level allow sets OR-ed into the rows they select
 #pragma once
+#include "kano_pairwalk.hpp"
 #include "kano_prims.hpp"
 
 namespace kano {
@@ -86,127 +87,62 @@ __global__ __launch_bounds__(TPB) void k_ports_rows(int inplace, const uint8_t* 
 }
 
 // ---------------------------------------------------------------------------
-// Pair masks: the walk of k_pair_lane / k_pair_wave (kano_kernels.hpp: the
-// same tables, the same ownership rule for row shards, the same dead flags)
-// with out[q * KW + w] = OR of pmask[p * KW + w] over pols(i, j) instead of
-// a count.  The mask words are taken PM_CH at a time in registers (one walk
-// for up to 128 slots, ceil(KW / PM_CH) walks beyond).  One pair belongs to
-// one lane or one wave: no atomics.
+// Pair masks: the pair walk (kano_pairwalk.hpp) with out[q * KW + w] = OR of
+// pmask[p * KW + w] over the alive matching policies.  The mask words are
+// taken PM_CH at a time in registers (one walk for up to 128 slots,
+// ceil(KW / PM_CH) walks beyond).  One pair belongs to one lane or one wave:
+// no atomics.
 // ---------------------------------------------------------------------------
 struct PairMaskArgs {
-  const int32_t* pairs;  // (i, j) x Q
-  i64 Q;
-  const int32_t* rcls;   // null: the build had no policies (only the added part)
-  const int32_t* ccls;
-  const i64* soffc;
-  const int32_t* slist;
-  const uint8_t* dead;   // P + A flags; null: none removed
-  const u64* AC;
-  i64 ldC;
-  i64 P;
-  const u64* asel;
-  const u64* aalw;
-  i64 W, A;
-  i64 r0, r1;
+  PairTables t;          // (t.dead: the removed ids' flags)
   const u64* pmask;      // (P + A) x KW
   i64 KW;
   u64* out;              // Q x KW
 };
 constexpr int PM_CH = 2;
-// the wave form when a pair walks more than this many policies on average
-// (mean |S(c)| + added policies: k_pair_wave's threshold, PAIR_WAVE_MIN)
-constexpr i64 PMASK_WAVE_MIN = 16;
+
+// The mask words of pair q, PM_CH at a time: one list lookup, then a walk per
+// chunk over the positions k0, k0 + step, .. (WAVE: a lane's share, the lanes'
+// words OR-ed across the wave -- every lane of the wave arrives -- and lane 0
+// writing).
+template <bool WAVE>
+__device__ __forceinline__ void pm_pair(const PairMaskArgs& a, i64 q) {
+  const int lane = threadIdx.x & 63;
+  const i64 i = a.t.pairs[2 * q], j = a.t.pairs[2 * q + 1];
+  const bool own = pair_own(a.t, i);
+  i64 s0 = 0, s = 0, x = 0;
+  if (own) pair_list(a.t, i, j, s0, s, x);
+  for (i64 w0 = 0; w0 < a.KW; w0 += PM_CH) {
+    u64 acc[PM_CH];
+#pragma unroll
+    for (int c = 0; c < PM_CH; ++c) acc[c] = 0;
+    pair_walk(
+        a.t, i, j, own, s0, s, x, WAVE ? lane : 0, WAVE ? 64 : 1,
+        [&](i64 p) { return pair_alive(a.t.dead, p); },
+        [&](i64 p) {
+#pragma unroll
+          for (int c = 0; c < PM_CH; ++c)
+            if (w0 + c < a.KW) acc[c] |= a.pmask[p * a.KW + w0 + c];
+        });
+#pragma unroll
+    for (int c = 0; c < PM_CH; ++c) {
+      const u64 v = WAVE ? wave_or(acc[c]) : acc[c];
+      if ((!WAVE || lane == 0) && w0 + c < a.KW) a.out[q * a.KW + w0 + c] = v;
+    }
+  }
+}
 
 // a lane per pair, S(c) walked serially; grid-stride over the pairs
 __global__ __launch_bounds__(TPB) void k_pmask_lane(PairMaskArgs a) {
   const i64 stride = (i64)gridDim.x * TPB;
-  for (i64 q = (i64)blockIdx.x * TPB + threadIdx.x; q < a.Q; q += stride) {
-    const i64 i = a.pairs[2 * q], j = a.pairs[2 * q + 1];
-    const bool own = i >= a.r0 && i < a.r1;
-    i64 s0 = 0, s = 0, x = 0;
-    if (own && a.rcls) {
-      const int32_t c = a.rcls[i];
-      s0 = a.soffc[c];
-      s = a.soffc[c + 1] - s0;
-      x = a.ccls[j];
-    }
-    for (i64 w0 = 0; w0 < a.KW; w0 += PM_CH) {
-      u64 acc[PM_CH];
-#pragma unroll
-      for (int c = 0; c < PM_CH; ++c) acc[c] = 0;
-      for (i64 k = 0; k < s; ++k) {
-        const int32_t p = a.slist[s0 + k];
-        if (!(a.dead && a.dead[p]) && ((a.AC[(i64)p * a.ldC + (x >> 6)] >> (x & 63)) & 1ull)) {
-#pragma unroll
-          for (int c = 0; c < PM_CH; ++c)
-            if (w0 + c < a.KW) acc[c] |= a.pmask[(i64)p * a.KW + w0 + c];
-        }
-      }
-      for (i64 t = 0; own && t < a.A; ++t) {
-        if (!(a.dead && a.dead[a.P + t]) && ((a.asel[t * a.W + (i >> 6)] >> (i & 63)) & 1ull) &&
-            ((a.aalw[t * a.W + (j >> 6)] >> (j & 63)) & 1ull)) {
-#pragma unroll
-          for (int c = 0; c < PM_CH; ++c)
-            if (w0 + c < a.KW) acc[c] |= a.pmask[(a.P + t) * a.KW + w0 + c];
-        }
-      }
-#pragma unroll
-      for (int c = 0; c < PM_CH; ++c)
-        if (w0 + c < a.KW) a.out[q * a.KW + w0 + c] = acc[c];
-    }
-  }
+  for (i64 q = (i64)blockIdx.x * TPB + threadIdx.x; q < a.t.Q; q += stride) pm_pair<false>(a, q);
 }
 
-__device__ __forceinline__ u64 wave_or(u64 x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x |= __shfl_xor(x, o, 64);
-  return x;
-}
-
-// a wave per pair, the lanes striding S(c) and the added policies, the lanes'
-// words OR-ed across the wave; wave gw of nw takes a contiguous run of pairs
+// a wave per pair, the lanes striding S(c) and the added policies
 __global__ __launch_bounds__(TPB) void k_pmask_wave(PairMaskArgs a) {
-  const int lane = threadIdx.x & 63;
-  const i64 nw = (i64)gridDim.x * (TPB / 64), gw = (i64)blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
-  const i64 per = (a.Q + nw - 1) / nw;
-  const i64 q1 = min(a.Q, (gw + 1) * per);
-  for (i64 q = gw * per; q < q1; ++q) {          // wave-uniform
-    const i64 i = a.pairs[2 * q], j = a.pairs[2 * q + 1];
-    const bool own = i >= a.r0 && i < a.r1;
-    i64 s0 = 0, s = 0, x = 0;
-    if (own && a.rcls) {
-      const int32_t c = a.rcls[i];
-      s0 = a.soffc[c];
-      s = a.soffc[c + 1] - s0;
-      x = a.ccls[j];
-    }
-    for (i64 w0 = 0; w0 < a.KW; w0 += PM_CH) {
-      u64 acc[PM_CH];
-#pragma unroll
-      for (int c = 0; c < PM_CH; ++c) acc[c] = 0;
-      for (i64 k = lane; k < s; k += 64) {
-        const int32_t p = a.slist[s0 + k];
-        if (!(a.dead && a.dead[p]) && ((a.AC[(i64)p * a.ldC + (x >> 6)] >> (x & 63)) & 1ull)) {
-#pragma unroll
-          for (int c = 0; c < PM_CH; ++c)
-            if (w0 + c < a.KW) acc[c] |= a.pmask[(i64)p * a.KW + w0 + c];
-        }
-      }
-      for (i64 t = lane; own && t < a.A; t += 64) {
-        if (!(a.dead && a.dead[a.P + t]) && ((a.asel[t * a.W + (i >> 6)] >> (i & 63)) & 1ull) &&
-            ((a.aalw[t * a.W + (j >> 6)] >> (j & 63)) & 1ull)) {
-#pragma unroll
-          for (int c = 0; c < PM_CH; ++c)
-            if (w0 + c < a.KW) acc[c] |= a.pmask[(a.P + t) * a.KW + w0 + c];
-        }
-      }
-#pragma unroll
-      for (int c = 0; c < PM_CH; ++c) {
-        const u64 v = wave_or(acc[c]);             // (every lane of the wave arrives)
-        if (lane == 0 && w0 + c < a.KW) a.out[q * a.KW + w0 + c] = v;
-      }
-    }
-  }
+  i64 q0, q1;
+  wave_pair_run(a.t.Q, q0, q1);
+  for (i64 q = q0; q < q1; ++q) pm_pair<true>(a, q);   // wave-uniform
 }
 
 }  // namespace kano

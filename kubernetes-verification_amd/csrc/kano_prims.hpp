@@ -65,6 +65,12 @@ __device__ __forceinline__ T wave_sum(T x) {
   return x;
 }
 
+__device__ __forceinline__ u64 wave_or(u64 x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x |= __shfl_xor(x, o, 64);
+  return x;
+}
+
 // exclusive scan over the 64 lanes of a wave; total = sum of all lanes
 template <typename T>
 __device__ __forceinline__ T wave_excl_scan(T v, T& total) {

@@ -21,6 +21,7 @@
 //                    the rows they select, resolved bit by bit with the walk
 //                    of the pair kernels below
 #pragma once
+#include "kano_pairwalk.hpp"
 #include "kano_prims.hpp"
 
 namespace kano {
@@ -127,33 +128,16 @@ __global__ __launch_bounds__(TPB) void k_verdict_class(i64 U, const i64* __restr
 }
 
 // ---------------------------------------------------------------------------
-// The walk of one pair: k_pmask_lane / k_pmask_wave's (kano_ports.hpp: the same
-// tables, the same ownership rule for row shards, the dead flags inside the
-// keys) tracking the running (best rank, deny seen at best, smallest allow id
-// at best, smallest deny id at best); all of it resets when a lower rank
-// matches.  One pair belongs to one lane or one wave: no atomics.
+// The verdict of one pair: the pair walk (kano_pairwalk.hpp; the dead flags
+// are inside the keys) tracking the running (best rank, deny seen at best,
+// smallest allow id at best, smallest deny id at best); all of it resets when
+// a lower rank matches.  One pair belongs to one lane or one wave: no atomics.
 // ---------------------------------------------------------------------------
 struct VerdictArgs {
-  const int32_t* pairs;  // (i, j) x Q
-  i64 Q;
-  const int32_t* rcls;   // null: the build had no policies (only the added part)
-  const int32_t* ccls;
-  const i64* soffc;
-  const int32_t* slist;
-  const uint32_t* key;   // P + A keys
-  const u64* AC;
-  i64 ldC;
-  i64 P;
-  const u64* asel;
-  const u64* aalw;
-  i64 W, A;
-  i64 r0, r1;
+  PairTables t;          // (t.key: the ids' keys)
   uint32_t* out_key;     // Q: best rank * 2 + deny, VD_NONE where nothing matches
   int32_t* out_id;       // Q: the deciding engine id, -1 where nothing matches
 };
-// the wave form when a pair walks more than this many policies on average
-// (k_pair_wave's and k_pmask_wave's threshold)
-constexpr i64 VERDICT_WAVE_MIN = 16;
 
 struct VdState {
   uint32_t best = VD_NONE;
@@ -178,27 +162,14 @@ __device__ __forceinline__ void vd_take(VdState& s, uint32_t k, int32_t p) {
   }
 }
 
-// the matching policies of (i, j) at positions k0, k0 + step, .. of S(rc(i))
-// and of the added policies (own: this context holds row i)
+// the state over the walk's positions k0, k0 + step, .. (own: this context
+// holds row i)
 __device__ __forceinline__ VdState vd_walk(const VerdictArgs& a, i64 i, i64 j, bool own, i64 k0,
                                            i64 step) {
   VdState s;
-  if (!own) return s;
-  if (a.rcls) {
-    const int32_t c = a.rcls[i];
-    const i64 s0 = a.soffc[c], n = a.soffc[c + 1] - s0, x = a.ccls[j];
-    for (i64 k = k0; k < n; k += step) {
-      const int32_t p = a.slist[s0 + k];
-      const uint32_t kp = a.key[p];
-      if (kp != VD_DEAD && ((a.AC[(i64)p * a.ldC + (x >> 6)] >> (x & 63)) & 1ull)) vd_take(s, kp, p);
-    }
-  }
-  for (i64 t = k0; t < a.A; t += step) {
-    const uint32_t kp = a.key[a.P + t];
-    if (kp != VD_DEAD && ((a.asel[t * a.W + (i >> 6)] >> (i & 63)) & 1ull) &&
-        ((a.aalw[t * a.W + (j >> 6)] >> (j & 63)) & 1ull))
-      vd_take(s, kp, (int32_t)(a.P + t));
-  }
+  pair_walk(
+      a.t, i, j, own, k0, step, [&](i64 p) { return a.t.key[p] != VD_DEAD; },
+      [&](i64 p) { vd_take(s, a.t.key[p], (int32_t)p); });
   return s;
 }
 
@@ -211,23 +182,21 @@ __device__ __forceinline__ void vd_store(const VerdictArgs& a, i64 q, const VdSt
 // a lane per pair, S(c) walked serially; grid-stride over the pairs
 __global__ __launch_bounds__(TPB) void k_verdict_lane(VerdictArgs a) {
   const i64 stride = (i64)gridDim.x * TPB;
-  for (i64 q = (i64)blockIdx.x * TPB + threadIdx.x; q < a.Q; q += stride) {
-    const i64 i = a.pairs[2 * q], j = a.pairs[2 * q + 1];
-    vd_store(a, q, vd_walk(a, i, j, i >= a.r0 && i < a.r1, 0, 1));
+  for (i64 q = (i64)blockIdx.x * TPB + threadIdx.x; q < a.t.Q; q += stride) {
+    const i64 i = a.t.pairs[2 * q], j = a.t.pairs[2 * q + 1];
+    vd_store(a, q, vd_walk(a, i, j, pair_own(a.t, i), 0, 1));
   }
 }
 
 // a wave per pair, the lanes striding S(c) and the added policies, their
-// states met by a butterfly (the lower rank wins, equal ranks merge); wave gw
-// of nw takes a contiguous run of pairs
+// states met by a butterfly (the lower rank wins, equal ranks merge)
 __global__ __launch_bounds__(TPB) void k_verdict_wave(VerdictArgs a) {
   const int lane = threadIdx.x & 63;
-  const i64 nw = (i64)gridDim.x * (TPB / 64), gw = (i64)blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
-  const i64 per = (a.Q + nw - 1) / nw;
-  const i64 q1 = min(a.Q, (gw + 1) * per);
-  for (i64 q = gw * per; q < q1; ++q) {            // wave-uniform
-    const i64 i = a.pairs[2 * q], j = a.pairs[2 * q + 1];
-    VdState s = vd_walk(a, i, j, i >= a.r0 && i < a.r1, lane, 64);
+  i64 q0, q1;
+  wave_pair_run(a.t.Q, q0, q1);
+  for (i64 q = q0; q < q1; ++q) {                  // wave-uniform
+    const i64 i = a.t.pairs[2 * q], j = a.t.pairs[2 * q + 1];
+    VdState s = vd_walk(a, i, j, pair_own(a.t, i), lane, 64);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {               // (every lane of the wave arrives)
       VdState u;
@@ -256,12 +225,12 @@ __global__ __launch_bounds__(TPB) void k_verdict_wave(VerdictArgs a) {
 __global__ __launch_bounds__(TPB) void k_verdict_rows(VerdictArgs a,
                                                       const int32_t* __restrict__ rows, i64 n,
                                                       u64* __restrict__ M, i64 ldM) {
-  const i64 r = rows[blockIdx.x], i = a.r0 + r;
+  const i64 r = rows[blockIdx.x], i = a.t.r0 + r;
   const int lane = threadIdx.x & 63;
   for (i64 w = threadIdx.x >> 6; w < ldM; w += TPB / 64) {   // wave-uniform
     const i64 j = w * 64 + lane;
     bool bit = false;
-    if (w < a.W && j < n) {
+    if (w < a.t.W && j < n) {
       const VdState s = vd_walk(a, i, j, true, 0, 1);
       bit = s.best != VD_NONE && !s.dn;
     }
