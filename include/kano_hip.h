@@ -806,6 +806,59 @@ int kano_set_expressions(kano_ctx* ctx, int32_t E, const int32_t* col, const int
 #define KANO_K8S_DST_EG 8
 int kano_k8s_edge(kano_ctx* in_t, kano_ctx* eg_t, kano_ctx* dst, int flags, int64_t* info);
 
+/* k8s.connectivity: the reading of NetworkPolicies a cluster enforces
+ * (networking.k8s.io/v1), from two class-level builds the host compiles
+ * (kano/k8s.py compile_conformant): eg holds E[src][dst] (an entry selects an
+ * Egress-typed policy's pods and allows one peer of one rule), in holds
+ * I[dst][src] likewise for Ingress.  Every policy of a type contributes an
+ * entry, so a pod is isolated in a direction iff some entry of that build
+ * selects it.  dst's rows :=
+ *   allowed[s][d] = (s == d and flags & KANO_K8S_CONN_SELF)
+ *                 | (!isoE[s] | E'[s][d]) & (!isoI[d] | I'[d][s])
+ * with E' / I' over the kept entries only (keep_e / keep_i: one flag per
+ * engine id, NULL keeps all -- a port query keeps the entries whose rule
+ * counts on that port); isolation always reads every entry.
+ * eg and in are full, unedited builds (kano_build_classes: their matrices are
+ * neither read nor written); only their class tables are read.  A source
+ * without policies has no classes and constrains nothing: that side is all
+ * ones.  dst is a matrix context of the same n and device (an empty build),
+ * optionally a row shard (kano_set_shard): every word of every held row is
+ * written, bits at positions >= n and the words W .. ldM - 1 are zero, and
+ * dst then reads as an edited matrix, like kano_policy_subset's destination.
+ * The rows of row shards concatenate.
+ * info (nullable) = [egress-isolated pods, ingress-isolated pods, kept egress
+ * entries, kept ingress entries]; the first two are counted by the run (two
+ * small launches, left out with info NULL) and stay 0 when nothing is
+ * launched.
+ * kano_k8s_isolated: out[i] = 1 iff some policy of ctx's build selects pod i
+ * (the row class's list is not empty), computed on the device, one copy.
+ * -EINVAL: a NULL context (or out), dst equal to a source, contexts of
+ * different devices or n, nids_e / nids_i other than the sources' P;
+ * -ENOTSUP: a source holding a row shard, policy lists, added or removed
+ * policies or edited rows, more than 4,194,240 held rows; -ENOMEM (with a
+ * message): a device buffer could not be allocated.  kano_k8s_conn reports its
+ * errors on dst; the contexts stay usable after every error.  n == 0 or no
+ * held rows launch nothing.  The device buffers are the call's own (the keep
+ * flags, the class-level rows Re, Ri and Ri transposed), freed on return; the
+ * sources' tables and stored results are unchanged.  Exact bits.
+ * Two forms write the same bits: direct (every held row gathered from the two
+ * class-level tables) and streamed (both tables' class rows expanded to pod
+ * words once, then M[s] = XE[rc_e(s)] & XT[cc_i(s)]; taken when the class rows
+ * number at most half the held rows, as kano_k8s_edge takes its own).
+ * KANO_K8S_CONN_DIRECT / KANO_K8S_CONN_STREAM force one (a table of more than
+ * 4,194,240 class rows is never streamed, whatever the flag). */
+#define KANO_K8S_CONN_SELF 1
+#define KANO_K8S_CONN_DIRECT 2
+#define KANO_K8S_CONN_STREAM 4
+int kano_k8s_conn(kano_ctx* eg, kano_ctx* in, kano_ctx* dst, int flags,
+                  int64_t nids_e, const uint8_t* keep_e /* nids_e, nullable: all */,
+                  int64_t nids_i, const uint8_t* keep_i /* nids_i, nullable: all */,
+                  int64_t* info /* 4, nullable */);
+int kano_k8s_isolated(kano_ctx* ctx, uint8_t* out /* n */);
+/* KANO_TUNE timing=1: the last kano_k8s_conn's device time in ms on its
+ * destination (the fills and the kernels, no copies), else 0. */
+int kano_k8s_conn_time(kano_ctx* ctx, float* ms);
+
 /* kano_build without the matrix write (model.py:125-165 up to the class-level
  * matrix Mc, the lists and the column checks): M is written on first use
  * (kano_get_rows, kano_path, ...).  For sources of kano_k8s_edge, which reads

@@ -317,6 +317,9 @@ struct kano_ctx {
   // (kano_verdict_matrix leaves its time on the source and on the destination)
   float verdict_ms = 0.f;     // timing=1: the last kano_verdict_matrix's fills + kernels
   float pverdict_ms = 0.f;    // timing=1: the last kano_pair_verdicts' kernel
+  // k8s.connectivity (kano_k8s_conn, in the destination context): the device
+  // buffers are the call's own; only the time stays
+  float conn_ms = 0.f;        // timing=1: the last kano_k8s_conn's fills + kernels
   // policy_shadow count-only (kano_verify with shadow_cap < 0): the grouped
   // count (k_shg_*) instead of the pair-by-pair flags
   bool vs_count_only = false;

@@ -7,6 +7,7 @@
 #include "kano_engine.hpp"
 #include "kano_inc.hpp"
 #include "kano_k8s.hpp"
+#include "kano_k8s_conn.hpp"
 #include "kano_path.hpp"
 #include "kano_hops.hpp"
 #include "kano_intents.hpp"
@@ -2087,6 +2088,226 @@ int kano_verdict_matrix_time(kano_ctx* ctx, float* ms) {
 int kano_pair_verdicts_time(kano_ctx* ctx, float* ms) {
   if (!ctx || !ms) return -EINVAL;
   *ms = ctx->pverdict_ms;
+  return 0;
+}
+
+}  // extern "C"
+
+// ===========================================================================
+// k8s.connectivity: the Kubernetes reading of NetworkPolicies from an egress
+// and an ingress class-level build (k_conn_*, kano_k8s_conn.hpp).  Only the
+// sources' class tables are read (soffc / slist, AC, Mc, the pods' class ids);
+// their matrices are neither read nor written.
+// ===========================================================================
+namespace {
+
+// a source: a full, unedited class-level build.  Errors go to err_ctx.
+int conn_source(kano_ctx* s, kano_ctx* err_ctx, const char* what) {
+  const std::string w(what);
+  const int rc = ensure_built(s);
+  if (rc) return s == err_ctx ? rc : fail(err_ctx, rc, w + ": source: " + s->err);
+  if (s->lists_mode) return fail(err_ctx, -ENOTSUP, w + ": a source holds policy lists");
+  if (s->r0 != 0 || s->r1 != s->n)
+    return fail(err_ctx, -ENOTSUP, w + ": a source holds a row shard (needs every row)");
+  if (s->inc_A > 0 || std::find(s->dead.begin(), s->dead.end(), 1) != s->dead.end())
+    return fail(err_ctx, -ENOTSUP, w + ": a source holds added or removed policies");
+  if (s->rows_dirty || s->user_edited)
+    return fail(err_ctx, -ENOTSUP, w + ": a source holds edited rows");
+  return 0;
+}
+
+// without policies a build has no classes: that direction constrains nothing
+bool conn_classes(const kano_ctx* s) { return s->P > 0 && s->rc.U > 0 && s->cc.U > 0; }
+
+}  // namespace
+
+extern "C" {
+
+int kano_k8s_conn(kano_ctx* eg, kano_ctx* in, kano_ctx* dst, int flags, int64_t nids_e,
+                  const uint8_t* keep_e, int64_t nids_i, const uint8_t* keep_i, int64_t* info) {
+  if (!eg || !in || !dst) return -EINVAL;
+  const char* const what = "kano_k8s_conn";
+  if (dst == eg || dst == in)
+    return fail(dst, -EINVAL, "kano_k8s_conn: the destination must be another context");
+  if (eg->device != dst->device || in->device != dst->device)
+    return fail(dst, -EINVAL, "kano_k8s_conn: contexts on two devices");
+  kano_ctx* ctx = dst;
+  KCHK(hipSetDevice(dst->device));
+  KTRY(conn_source(eg, dst, what));
+  KTRY(conn_source(in, dst, what));
+  KTRY(ensure_matrix(dst));
+  const i64 n = dst->n, W = dst->W, ldM = dst->ldM, r0 = dst->r0, rl = rows_local(dst);
+  if (eg->n != n || in->n != n)
+    return fail(dst, -EINVAL, "kano_k8s_conn: the three contexts must hold the same pods");
+  if (nids_e != eg->P || nids_i != in->P)
+    return fail(dst, -EINVAL, "kano_k8s_conn: nids = " + std::to_string(nids_e) + " / " +
+                                  std::to_string(nids_i) + ", the sources have " +
+                                  std::to_string(eg->P) + " / " + std::to_string(in->P) +
+                                  " engine ids");
+  if ((rl + K8S_XR - 1) / K8S_XR > 65535)   // (k_conn_expand's grid)
+    return fail(dst, -ENOTSUP, "kano_k8s_conn: more than 4,194,240 rows in one context");
+  for (kano_ctx* s : {eg, in}) {
+    const int rc = sync(s);   // the sources' classes are complete
+    if (rc) return fail(dst, rc, "kano_k8s_conn: source: " + s->err);
+  }
+  const bool hasE = conn_classes(eg), hasI = conn_classes(in);
+  i64 kept[2] = {0, 0};
+  for (i64 p = 0; p < nids_e; ++p) kept[0] += keep_e ? keep_e[p] != 0 : 1;
+  for (i64 p = 0; p < nids_i; ++p) kept[1] += keep_i ? keep_i[p] != 0 : 1;
+  unsigned long long iso[2] = {0, 0};
+  dst->conn_ms = 0.f;
+  DBuf ke, ki, re, ri, ti, xr, cnt;
+  auto run = [&]() -> int {
+    const i64 Ue = eg->rc.U, ldCe = eg->ldC, Ui = in->rc.U, Xi = in->cc.U, ldCi = in->ldC;
+    const i64 KWi = (Ui + 63) / 64;
+    KTRY(dalloc(ctx, cnt, sizeof(unsigned long long) * 2));
+    if (hasE) {
+      KTRY(dalloc(ctx, re, sizeof(u64) * (size_t)(Ue * ldCe)));
+      if (keep_e) {
+        KTRY(dalloc(ctx, ke, (size_t)nids_e));
+        KCHK(hipMemcpyAsync(ke.p, keep_e, (size_t)nids_e, hipMemcpyHostToDevice, ctx->stream));
+      }
+    }
+    if (hasI) {
+      KTRY(dalloc(ctx, ri, sizeof(u64) * (size_t)(Ui * ldCi)));
+      KTRY(dalloc(ctx, ti, sizeof(u64) * (size_t)(Xi * KWi)));
+      if (keep_i) {
+        KTRY(dalloc(ctx, ki, (size_t)nids_i));
+        KCHK(hipMemcpyAsync(ki.p, keep_i, (size_t)nids_i, hipMemcpyHostToDevice, ctx->stream));
+      }
+    }
+    // the streamed form when the class rows are few beside the held rows (as
+    // kano_k8s_edge picks it), or as the flags force
+    const i64 Us = (hasE ? Ue : 0) + (hasI ? Xi : 0);
+    // (its class-row expansions' grids hold at most 65535 * 64 class rows a
+    // table: beyond that the direct form, whatever the flags say)
+    const i64 xmax = (i64)65535 * K8S_XR;
+    const bool stream = Us > 0 && !(flags & KANO_K8S_CONN_DIRECT) &&
+                        (!hasE || Ue <= xmax) && (!hasI || Xi <= xmax) &&
+                        ((flags & KANO_K8S_CONN_STREAM) || Us <= std::max<i64>(rl / 2, 1));
+    if (stream) KTRY(dalloc(ctx, xr, sizeof(u64) * (size_t)(Us * ldM)));
+    EventPair<> tev;
+    if (dst->stage_timing) KTRY(tev.start(ctx));
+    KCHK(hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long) * 2, ctx->stream));
+    int k = 0;
+    for (kano_ctx* s : {eg, in}) {
+      const int side = k++;
+      if (!(side ? hasI : hasE)) continue;
+      int wl;
+      i64 cap;
+      derived_shape(ctx, s->ldC, &wl, &cap);
+      hipLaunchKernelGGL(k_conn_class, dim3((unsigned)std::min<i64>(s->rc.U, cap)), dim3(TPB), 0,
+                         ctx->stream, s->rc.U, (const i64*)P_<i64>(s->soffc),
+                         (const int32_t*)P_<int32_t>(s->slist),
+                         (const uint8_t*)(side ? ki.p : ke.p), (const u64*)P_<u64>(s->AC),
+                         (const u64*)P_<u64>(s->Mc), s->ldC, wl, P_<u64>(side ? ri : re));
+      KLAUNCH();
+      if (!info) continue;   // the isolated pods are counted for info only
+      hipLaunchKernelGGL(k_conn_isolated, dim3(nblk(n)), dim3(TPB), 0, ctx->stream,
+                         (const int32_t*)P_<int32_t>(s->rc.cls), (const i64*)P_<i64>(s->soffc), n,
+                         (uint8_t*)nullptr, P_<unsigned long long>(cnt) + side);
+      KLAUNCH();
+    }
+    if (hasI) {
+      const i64 CGi = ((Xi + 63) / 64 + 15) / 16;
+      hipLaunchKernelGGL(k_k8s_transpose, dim3(nblk(KWi * CGi, TPB / 64)), dim3(TPB), 0,
+                         ctx->stream, (const u64*)P_<u64>(ri), ldCi, Ui, KWi, CGi, Xi, P_<u64>(ti),
+                         KWi);
+      KLAUNCH();
+    }
+    const int self = (flags & KANO_K8S_CONN_SELF) ? 1 : 0;
+    const int32_t* rce = P_<int32_t>(eg->rc.cls);
+    const int32_t* cce = P_<int32_t>(eg->cc.cls);
+    const int32_t* cci = P_<int32_t>(in->cc.cls);
+    const int32_t* rci = P_<int32_t>(in->rc.cls);
+    if (stream) {
+      // the class rows of both tables expanded to pod words once (row r is
+      // class r, the other table absent, no diagonal), then streamed to the
+      // held rows (kernels picked through a pointer are launched by handle:
+      // see launch_marked)
+      u64* XE = hasE ? P_<u64>(xr) : nullptr;
+      u64* XT = hasI ? P_<u64>(xr) + (hasE ? Ue : 0) * ldM : nullptr;
+      const int32_t* const none = nullptr;
+      if (hasE) {
+        auto CONN_EXPAND = ldCe <= CONN_STAGE_W ? k_conn_expand<true> : k_conn_expand<false>;
+        hipExtLaunchKernelGGL(CONN_EXPAND, dim3(nblk(ldM, K8S_XW), nblk(Ue, K8S_XR)), dim3(TPB), 0,
+                              ctx->stream, nullptr, nullptr, 0, (const u64*)P_<u64>(re), ldCe,
+                              none, cce, (const u64*)nullptr, (i64)0, none, none, 0, (i64)0, Ue,
+                              n, W, XE, ldM);
+        KLAUNCH();
+      }
+      if (hasI) {
+        auto CONN_EXPAND = KWi <= CONN_STAGE_W ? k_conn_expand<true> : k_conn_expand<false>;
+        hipExtLaunchKernelGGL(CONN_EXPAND, dim3(nblk(ldM, K8S_XW), nblk(Xi, K8S_XR)), dim3(TPB), 0,
+                              ctx->stream, nullptr, nullptr, 0, (const u64*)nullptr, (i64)0, none,
+                              none, (const u64*)P_<u64>(ti), KWi, none, rci, 0, (i64)0, Xi, n, W,
+                              XT, ldM);
+        KLAUNCH();
+      }
+      hipLaunchKernelGGL(k_conn_rows, dim3(nblk(rl * (ldM / 2))), dim3(TPB), 0, ctx->stream,
+                         (const u64*)XE, rce, (const u64*)XT, cci, self, r0, rl, ldM,
+                         P_<u64>(dst->M));
+      KLAUNCH();
+    } else {
+      // class rows of <= CONN_STAGE_W words together are staged in LDS by the expansion
+      const bool stage = (hasE ? ldCe : 0) + (hasI ? KWi : 0) <= CONN_STAGE_W;
+      auto CONN_EXPAND = stage ? k_conn_expand<true> : k_conn_expand<false>;
+      hipExtLaunchKernelGGL(CONN_EXPAND, dim3(nblk(ldM, K8S_XW), nblk(rl, K8S_XR)), dim3(TPB), 0,
+                            ctx->stream, nullptr, nullptr, 0,
+                            (const u64*)(hasE ? P_<u64>(re) : nullptr), ldCe, rce, cce,
+                            (const u64*)(hasI ? P_<u64>(ti) : nullptr), KWi, cci, rci, self, r0,
+                            rl, n, W, P_<u64>(dst->M), ldM);
+      KLAUNCH();
+    }
+    KTRY(tev.stop(ctx, &dst->conn_ms));
+    KCHK(hipMemcpyAsync(iso, cnt.p, sizeof(iso), hipMemcpyDeviceToHost, ctx->stream));
+    return sync(ctx);
+  };
+  if (n > 0 && rl > 0) {
+    const int rc = run();
+    derived_end(dst, {&ke, &ki, &re, &ri, &ti, &xr, &cnt}, rc);
+    if (rc) return rc;
+  }
+  if (info) {
+    info[0] = (int64_t)iso[0];
+    info[1] = (int64_t)iso[1];
+    info[2] = kept[0];
+    info[3] = kept[1];
+  }
+  return 0;
+}
+
+int kano_k8s_isolated(kano_ctx* ctx, uint8_t* out) {
+  if (!ctx) return -EINVAL;
+  KCHK(hipSetDevice(ctx->device));
+  KTRY(conn_source(ctx, ctx, "kano_k8s_isolated"));
+  if (!out) return fail(ctx, -EINVAL, "kano_k8s_isolated: out is NULL");
+  const i64 n = ctx->n;
+  if (n == 0) return 0;
+  if (!conn_classes(ctx)) {
+    std::memset(out, 0, (size_t)n);
+    return 0;
+  }
+  DBuf flag, cnt;
+  auto run = [&]() -> int {
+    KTRY(dalloc(ctx, flag, (size_t)n));
+    KTRY(dalloc(ctx, cnt, sizeof(unsigned long long)));
+    KCHK(hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long), ctx->stream));
+    hipLaunchKernelGGL(k_conn_isolated, dim3(nblk(n)), dim3(TPB), 0, ctx->stream,
+                       (const int32_t*)P_<int32_t>(ctx->rc.cls), (const i64*)P_<i64>(ctx->soffc),
+                       n, P_<uint8_t>(flag), P_<unsigned long long>(cnt));
+    KLAUNCH();
+    KCHK(hipMemcpyAsync(out, flag.p, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    return sync(ctx);
+  };
+  const int rc = run();
+  free_temps(ctx, rc, {&flag, &cnt});
+  return rc;
+}
+
+int kano_k8s_conn_time(kano_ctx* ctx, float* ms) {
+  if (!ctx || !ms) return -EINVAL;
+  *ms = ctx->conn_ms;
   return 0;
 }
 

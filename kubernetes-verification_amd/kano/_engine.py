@@ -216,6 +216,44 @@ class DeviceBuild:
                   "kano_k8s_edge")
         return int(info[0])
 
+    def k8s_conn_from(self, eg: "DeviceBuild", ing: "DeviceBuild", allow_self: bool = True,
+                      keep_e=None, keep_i=None, form: str = "auto",
+                      counts: bool = True) -> Optional[dict]:
+        """This context's rows := the Kubernetes connectivity of the egress
+        and ingress class-level builds (kano_k8s_conn).  ``keep_e`` /
+        ``keep_i``: one flag per engine id of the build (None keeps all).
+        ``form``: "direct", "stream" or "auto" (the engine picks); the same bits.
+        ``counts``: return the call's info (the isolated pods, counted on the
+        device, and the kept entries); False skips the counting and returns None."""
+        fbits = (1 if allow_self else 0) | {"auto": 0, "direct": 2, "stream": 4}[form]
+        def flags_of(keep, src):
+            P = src.info()["P"]
+            if keep is None:
+                return P, None
+            k = np.ascontiguousarray(np.asarray(keep).reshape(-1) != 0, dtype=np.uint8)
+            return int(k.shape[0]), k
+        ne, ke = flags_of(keep_e, eg)
+        ni, ki = flags_of(keep_i, ing)
+        info = np.zeros(4, dtype=np.int64) if counts else None
+        self._chk(self.lib.kano_k8s_conn(eg.ctx, ing.ctx, self.ctx, fbits, ne, _ptr(ke), ni,
+                                         _ptr(ki), _ptr(info)), "kano_k8s_conn")
+        if info is None:
+            return None
+        return dict(zip(("egress_isolated", "ingress_isolated", "egress_entries",
+                         "ingress_entries"), map(int, info)))
+
+    def k8s_isolated(self) -> np.ndarray:
+        """Per pod: some policy of this build selects it (kano_k8s_isolated)."""
+        out = np.zeros(self.n, dtype=np.uint8)
+        self._chk(self.lib.kano_k8s_isolated(self.ctx, _ptr(out)), "kano_k8s_isolated")
+        return out.astype(bool)
+
+    def k8s_conn_time(self) -> float:
+        """The last k8s_conn_from's device time (ms; KANO_TUNE=timing=1)."""
+        ms = ctypes.c_float(0.0)
+        self._chk(self.lib.kano_k8s_conn_time(self.ctx, byref(ms)), "kano_k8s_conn_time")
+        return float(ms.value)
+
     def path_shard_words(self) -> int:
         w = c_int64(0)
         self._chk(self.lib.kano_path_shard_words(self.ctx, byref(w)), "kano_path_shard_words")

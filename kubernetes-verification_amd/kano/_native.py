@@ -104,6 +104,10 @@ SIGNATURES = {
     "kano_set_expressions": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "kano_path": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "kano_k8s_edge": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "kano_k8s_conn": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int64,
+                              c_void_p, c_void_p]),
+    "kano_k8s_isolated": (c_int, [c_void_p, c_void_p]),
+    "kano_k8s_conn_time": (c_int, [c_void_p, POINTER(c_float)]),
     "kano_build_classes": (c_int, [c_void_p, c_int]),
     "kano_path_shard_words": (c_int, [c_void_p, POINTER(c_int64)]),
     "kano_path_shard": (c_int, [c_void_p, c_void_p]),

@@ -67,6 +67,12 @@ departures, both z3 sort/name artefacts rather than readings of the rules):
 Parity: against ``oracle/kano_oracle.py kubesv_edge_py``, a restatement of
 the Datalog rules on Python sets -- unpinned against kubesv itself (it needs
 z3 and the kubernetes client, both absent here).
+
+The reading a cluster enforces (networking.k8s.io/v1: policyTypes, isolation
+per direction, namespaced peers, ports) is the second half of this module:
+``connectivity`` / ``compile_conformant`` / ``load_manifests``, over the same
+objects.  ``build``, ``compile_policies`` and kubesv's quirks are untouched by
+it.
 """
 from __future__ import annotations
 
@@ -374,3 +380,376 @@ def build(pods: List[Pod], policies: List[NetworkPolicy], namespaces: List[Names
     info = {"ingress_policies": len(ing), "egress_policies": len(egr),
             "product_bits": added, "all_pairs": all_pairs, "rows": rows}
     return K8sReachability(_wrap(out, n), _wrap(in_t, n), _wrap(eg_t, n), selected, info)
+
+
+# ---------------------------------------------------------------------------
+# The conformant reading (networking.k8s.io/v1): what a cluster enforces.
+#
+# Policy P of namespace N selects the pods of N matching spec.podSelector.
+# Its types are spec.policyTypes as listed, or -- absent -- Ingress plus Egress
+# iff the spec has an ``egress`` key.  A pod is egress-isolated iff some
+# Egress-typed policy selects it (ingress likewise); isolation never depends
+# on rules or ports.  A rule with an absent or empty ``from`` / ``to`` matches
+# every pod; a peer's bare podSelector stays in N, a bare namespaceSelector
+# takes every pod of the matching namespaces, both narrow each other, a peer
+# with neither selector is every pod of N and an ipBlock peer is no pod.
+#   allowed[s, d] = (allow_self and s == d)
+#                   or ((not isoE[s] or E[s, d]) and (not isoI[d] or I[d, s]))
+# Selectors AND matchLabels and matchExpressions (In, NotIn, Exists,
+# DoesNotExist; anything else is a ValueError); a term on a key no pod (no
+# namespace a pod lives in) carries is resolved here, before the engine sees
+# it: matchLabels / In / Exists match nothing, NotIn / DoesNotExist always
+# hold -- so neither kano's quirk Q1 nor kubesv's quick fail (K2) applies.
+#
+# Out of scope: named ports (a string ``port`` never matches a numeric query),
+# ipBlock reachability (the matrix is pod to pod), AdminNetworkPolicy
+# (kano.algorithm.verdict_matrix is the tool for tiers), host-network pods and
+# sources with incremental updates (the two builds are made here, once).
+# ---------------------------------------------------------------------------
+
+_CONF_OPS = {"In": In, "NotIn": NotIn, "Exists": Exists, "DoesNotExist": DoesNotExist}
+_NS_LABEL = "__k8s_ns_label__"
+
+
+def _conformant_terms(selector: Optional[Dict[str, Any]], known: set) -> Optional[List[tuple]]:
+    """The (key, requirement) terms of a selector over the keys in ``known``,
+    or None when it matches nothing.  Terms on other keys are resolved here."""
+    if not selector:
+        return []
+    out, nothing = [], False
+    for e in selector.get("matchExpressions") or []:
+        name = (e or {}).get("operator")
+        op = _CONF_OPS.get(name) if isinstance(name, str) else None
+        if op is None:
+            raise ValueError(f"matchExpressions operator {name!r}: expected In, NotIn, Exists "
+                             "or DoesNotExist")
+        key = e.get("key")
+        if key not in known:
+            nothing = nothing or op in (In, Exists)       # NotIn / DoesNotExist: always true
+        elif op in (In, NotIn):
+            out.append((key, op(e.get("values") or [])))
+        else:
+            out.append((key, op()))
+    for k, v in (selector.get("matchLabels") or {}).items():
+        if k not in known:
+            nothing = True
+        else:
+            out.append((k, v))
+    return None if nothing else out
+
+
+def policy_types(spec: Dict[str, Any]) -> List[str]:
+    """spec.policyTypes as listed; absent: Ingress, plus Egress iff the spec
+    has an ``egress`` key."""
+    types = spec.get("policyTypes")
+    if types is None:
+        types = ["Ingress"] + (["Egress"] if "egress" in spec else [])
+    return list(types)
+
+
+def rule_counts(ports, port) -> bool:
+    """Whether a rule with this ``ports`` list counts for the query ``port``
+    (None: every rule counts -- an upper bound over ports; else (protocol,
+    number)).  An entry's protocol defaults to TCP; a named port (a string)
+    never matches."""
+    if port is None or not ports:
+        return True
+    protocol, number = port
+    for e in ports:
+        e = e or {}
+        if (e.get("protocol") or "TCP") != protocol:
+            continue
+        p, end = e.get("port"), e.get("endPort")
+        if p is None:
+            return True
+        if isinstance(p, str):
+            continue
+        if (p <= number <= end) if end is not None else p == number:
+            return True
+    return False
+
+
+def _port_query(port):
+    if port is None:
+        return None
+    protocol, number = port
+    if not isinstance(protocol, str) or isinstance(number, (str, bool)):
+        raise ValueError("port must be None or (protocol, number)")
+    return protocol, int(number)
+
+
+class Conformant:
+    """compile_conformant's result: the pods as Containers, the two kano
+    policy lists (egress: E[src][dst]; ingress: I[dst][src]; select = the
+    policy's namespace and podSelector, allow = one peer), and per list entry
+    its ``origin`` (policy index, direction, rule index, peer index -- the peer
+    index None for a rule matching every pod, both None for the entry that
+    only isolates) and the rule's ``ports``."""
+
+    def __init__(self, containers, egress, ingress, origin_egress, origin_ingress,
+                 ports_egress, ports_ingress):
+        self.containers = containers
+        self.egress, self.ingress = egress, ingress
+        self.origin_egress, self.origin_ingress = origin_egress, origin_ingress
+        self.ports_egress, self.ports_ingress = ports_egress, ports_ingress
+
+    def keep(self, port):
+        """The keep masks (egress, ingress) of a port query: None for every
+        entry, else uint8 flags, one per entry."""
+        port = _port_query(port)
+        if port is None:
+            return None, None
+        return tuple(np.array([rule_counts(p, port) for p in ports], dtype=np.uint8)
+                     for ports in (self.ports_egress, self.ports_ingress))
+
+
+def compile_conformant(pods: List[Pod], policies: List[NetworkPolicy],
+                       namespaces: List[Namespace]) -> Conformant:
+    """The conformant reading as kano objects (see the section's comment).
+    Every policy of a type that selects a pod-bearing selector contributes at
+    least one entry per type, so "selected by some entry" is "isolated": a
+    policy of a type whose rules allow nothing gets one entry whose allow side
+    no pod meets (DoesNotExist on the namespace column, which every pod
+    carries).  A policy whose selector matches nothing isolates nobody and is
+    dropped; so is a peer that matches nothing."""
+    nam_map = {ns.name: i for i, ns in enumerate(namespaces)}
+    by_name = {ns.name: ns for ns in namespaces}
+    pod_keys = set()
+    for p in pods:
+        if p.namespace not in nam_map:
+            raise KeyError(p.namespace)
+        pod_keys.update(p.labels.keys())
+    ns_pod_keys = set()                  # namespace label keys some pod sees
+    for name in {p.namespace for p in pods}:
+        ns_pod_keys.update(by_name[name].labels.keys())
+
+    aliases: Dict[Any, Any] = {}
+    lists = {"egress": [], "ingress": []}
+    origin = {"egress": [], "ingress": []}
+    ports = {"egress": [], "ingress": []}
+    for pi, pol in enumerate(policies):
+        spec = pol.spec or {}
+        types = policy_types(spec)
+        st = _conformant_terms(spec.get("podSelector"), pod_keys)
+        sel = None
+        if st is not None and pol.namespace in nam_map:
+            sel = _TermDict(aliases)
+            sel.add(_NS, pol.namespace)
+            for k, r in st:
+                sel.add(k, r)
+        for direction, typ, side in (("egress", "Egress", "to"), ("ingress", "Ingress", "from")):
+            if typ not in types:
+                continue
+            entries = []                 # (allow terms, rule index, peer index, ports)
+            for ri, rule in enumerate(spec.get(direction) or []):
+                rule = rule or {}
+                peers = rule.get(side)
+                if not peers:
+                    entries.append(({}, ri, None, rule.get("ports")))
+                    continue
+                for pj, peer in enumerate(peers):
+                    peer = peer or {}
+                    nsel, psel = peer.get("namespaceSelector"), peer.get("podSelector")
+                    nst = _conformant_terms(nsel, ns_pod_keys)
+                    pt = _conformant_terms(psel, pod_keys)
+                    if peer.get("ipBlock") is not None or nst is None or pt is None:
+                        continue         # no pod
+                    alw = _TermDict(aliases)
+                    if nsel is None:
+                        alw.add(_NS, pol.namespace)
+                    for k, r in nst:
+                        alw.add((_NS_LABEL, k), r)
+                    for k, r in pt:
+                        alw.add(k, r)
+                    entries.append((alw.d, ri, pj, rule.get("ports")))
+            if sel is None:
+                continue                 # selects nothing: isolates nobody
+            if not entries:
+                entries.append(({_NS: DoesNotExist()}, None, None, None))
+            for alw, ri, pj, rp in entries:
+                lists[direction].append((sel.d, alw))
+                origin[direction].append((pi, direction, ri, pj))
+                ports[direction].append(rp)
+
+    containers = []
+    for p in pods:
+        lab = dict(p.labels)
+        lab[_NS] = p.namespace
+        for k, v in by_name[p.namespace].labels.items():
+            lab[(_NS_LABEL, k)] = v
+        for a, col in aliases.items():
+            if col in lab:
+                lab[a] = lab[col]
+        containers.append(Container(p.name, lab))
+
+    def kano(pairs):
+        return [Policy(f"k8s{q}", PolicySelect(s), PolicyAllow(a), PolicyEgress, None)
+                for q, (s, a) in enumerate(pairs)]
+    return Conformant(containers, kano(lists["egress"]), kano(lists["ingress"]),
+                      origin["egress"], origin["ingress"], ports["egress"], ports["ingress"])
+
+
+class K8sConnectivity:
+    """The conformant reading of one cluster, resident on the device."""
+
+    def __init__(self, allowed, egress, ingress, compiled, policies, port, allow_self, info,
+                 isolated, device, rows, form="auto"):
+        #: allowed[src, dst], a ReachabilityMatrix: every kano.algorithm query reads it
+        self.allowed = allowed
+        #: the wrapped class-level builds: E[src][dst] and I[dst][src]
+        self.egress, self.ingress = egress, ingress
+        #: per pod: some Egress-typed (Ingress-typed) policy selects it
+        self.egress_isolated, self.ingress_isolated = isolated
+        #: per entry of the builds: (policy index, direction, rule index, peer index)
+        self.origin_egress = compiled.origin_egress
+        self.origin_ingress = compiled.origin_ingress
+        self.port = port
+        self.allow_self = allow_self
+        self.info = info
+        self._compiled, self._policies, self._device, self._rows = compiled, policies, device, rows
+        self._form = form
+
+    def on_port(self, port) -> "K8sConnectivity":
+        """The same cluster on another port: a new keep mask over the two
+        resident builds and one kano_k8s_conn -- nothing is interned or
+        uploaded again."""
+        return _connect(self.egress, self.ingress, self._compiled, self._policies, port,
+                        self.allow_self, (self.egress_isolated, self.ingress_isolated),
+                        self._device, self._rows, self._form)
+
+    def explain(self, src: int, dst: int) -> dict:
+        """Why src may (not) talk to dst on this object's port: ``allowed``,
+        ``self`` (the pair is allowed as self traffic) and per direction
+        ``isolated`` and ``policies`` -- the (policy name, rule index, peer
+        index) of the counted rules allowing the pair (kano_pair_policies on
+        the two builds, filtered by the port's keep mask).  ``blocked_by``
+        names the directions that block the pair."""
+        src, dst = int(src), int(dst)
+        n = self.allowed.container_size
+        if not (0 <= src < n and 0 <= dst < n):
+            raise IndexError("bitarray index out of range")
+        keep = self._compiled.keep(self.port)
+        out = {"self": bool(self.allow_self and src == dst), "blocked_by": []}
+        for direction, m, pair, iso, org, kp in (
+                ("egress", self.egress, (src, dst), self.egress_isolated,
+                 self.origin_egress, keep[0]),
+                ("ingress", self.ingress, (dst, src), self.ingress_isolated,
+                 self.origin_ingress, keep[1])):
+            ids = []
+            if org:
+                r = m.engine.pair_policies([pair], lists=True)
+                ids = r["policies"][r["offsets"][0]:r["offsets"][1]].tolist()
+            pols = [(self._policies[org[p][0]].name, org[p][2], org[p][3]) for p in ids
+                    if kp is None or kp[p]]
+            isolated = bool(iso[pair[0]])
+            out[direction] = {"isolated": isolated, "policies": pols}
+            if isolated and not pols:
+                out["blocked_by"].append(direction)
+        out["allowed"] = out["self"] or not out["blocked_by"]
+        return out
+
+
+def _connect(egress, ingress, compiled, policies, port, allow_self, isolated, device, rows,
+             form="auto"):
+    from ._engine import DeviceBuild
+    n = len(compiled.containers)
+    port = _port_query(port)
+    keep_e, keep_i = compiled.keep(port)
+    out = DeviceBuild.empty(n, device=device, rows=rows)
+    # (the isolated pods are known from the builds: no counting on the device)
+    out.k8s_conn_from(egress.engine, ingress.engine, allow_self, keep_e, keep_i, form,
+                      counts=False)
+    info = {"egress_entries": len(compiled.egress), "ingress_entries": len(compiled.ingress),
+            "kept_egress_entries": (len(compiled.egress) if keep_e is None
+                                    else int(np.count_nonzero(keep_e))),
+            "kept_ingress_entries": (len(compiled.ingress) if keep_i is None
+                                     else int(np.count_nonzero(keep_i))),
+            "egress_isolated": int(np.count_nonzero(isolated[0])),
+            "ingress_isolated": int(np.count_nonzero(isolated[1])),
+            "port": port, "allow_self": bool(allow_self), "rows": rows}
+    return K8sConnectivity(_wrap(out, n), egress, ingress, compiled, policies, port,
+                           bool(allow_self), info, isolated, device, rows, form)
+
+
+def connectivity(pods: List[Pod], policies: List[NetworkPolicy], namespaces: List[Namespace],
+                 port=None, allow_self: bool = True, device: int = 0, path: str = "auto",
+                 rows: Optional[tuple] = None, form: str = "auto") -> K8sConnectivity:
+    """The connectivity a cluster enforces (networking.k8s.io/v1) as an n x n
+    matrix on the device (rows src, columns dst).  ``port``: None -- every
+    rule counts whatever its ports, an upper bound over ports -- or
+    (protocol, number).  ``allow_self``: a pod always reaches itself.
+    ``rows=(r0, r1)``: only those rows (a multi-GPU rank's shard).  ``form``:
+    how the rows are written -- "direct" (gathered from the two class-level
+    tables), "stream" (the tables' class rows expanded once, then streamed) or
+    "auto" (streamed when the class rows are few beside the rows); the same
+    bits."""
+    from ._engine import DeviceBuild
+    from ._intern import intern
+    if form not in ("auto", "direct", "stream"):
+        raise ValueError(f"form must be 'auto', 'direct' or 'stream', not {form!r}")
+    policies = list(policies)
+    compiled = compile_conformant(pods, policies, namespaces)
+
+    def operand(pols):
+        b = DeviceBuild(intern(compiled.containers, pols), device=device, path=path, build=False)
+        b.build_classes(path)          # the class tables only: M is never written
+        return b
+
+    eg, ing = operand(compiled.egress), operand(compiled.ingress)
+    isolated = (eg.k8s_isolated(), ing.k8s_isolated())
+    n = len(pods)
+    return _connect(_wrap(eg, n), _wrap(ing, n), compiled, policies, port, allow_self, isolated,
+                    device, rows, form)
+
+
+_NS_NAME_LABEL = "kubernetes.io/metadata.name"
+
+
+def load_manifests(paths):
+    """(pods, policies, namespaces) from files or directories (their *.yaml,
+    *.yml and *.json files, sorted) of multi-document YAML: kinds Pod,
+    Namespace, NetworkPolicy and the items of a ``List``; other kinds are
+    ignored.  A namespace that is referenced but not declared is created, and
+    every namespace gets the ``kubernetes.io/metadata.name`` label if it lacks
+    it."""
+    import os
+    import yaml
+    if isinstance(paths, (str, os.PathLike)):
+        paths = [paths]
+    files = []
+    for p in paths:
+        p = os.fspath(p)
+        if os.path.isdir(p):
+            for root, dirs, names in os.walk(p):
+                dirs.sort()
+                files += [os.path.join(root, f) for f in sorted(names)
+                          if f.endswith((".yaml", ".yml", ".json"))]
+        else:
+            files.append(p)
+    pods, pols, nss = [], [], {}
+
+    def take(obj):
+        if not isinstance(obj, dict):
+            return
+        kind = obj.get("kind")
+        if isinstance(kind, str) and kind.endswith("List") and isinstance(obj.get("items"), list):
+            for it in obj["items"]:
+                take(it)
+        elif kind == "Pod":
+            pods.append(from_dict("Pod", obj))
+        elif kind == "NetworkPolicy":
+            pols.append(from_dict("NetworkPolicy", obj))
+        elif kind == "Namespace":
+            ns = from_dict("Namespace", obj)
+            nss[ns.name] = ns
+
+    for f in files:
+        with open(f) as fh:
+            for doc in yaml.safe_load_all(fh):
+                take(doc)
+    for o in pods + pols:
+        if o.namespace not in nss:
+            nss[o.namespace] = Namespace(o.namespace)
+    for ns in nss.values():
+        ns.labels.setdefault(_NS_NAME_LABEL, ns.name)
+    return pods, pols, list(nss.values())

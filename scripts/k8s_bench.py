@@ -4,7 +4,9 @@ namespace, one NetworkPolicy per (namespace, app) that admits ingress from a
 few apps of its namespace and of namespaces with a team label, and sends
 egress to a few apps -- timed per stage.  One JSON line per size.
 
-Usage: python scripts/k8s_bench.py [--pods 10000 100000] [--reps 3]"""
+Usage: python scripts/k8s_bench.py [--pods 10000 100000] [--reps 3]
+       python scripts/k8s_bench.py --conn ...   (the conformant reading,
+       kano.k8s.connectivity, over the same cluster)"""
 import argparse
 import json
 import os
@@ -50,8 +52,78 @@ def cluster(n, seed=0):
     return pods, pols, nss
 
 
+HBM_SPEC = 8.0e12   # MI355X HBM3E, bytes per second
+
+
+def conn(args):
+    """--conn: the same cluster read conformantly (kano.k8s.connectivity's
+    steps): the two class builds, then kano_k8s_conn -- its wall time, its
+    device time (kano_k8s_conn_time, KANO_TUNE timing=1) and the write's
+    fraction of the HBM spec for the matrix's n * n / 8 bytes."""
+    os.environ["KANO_TUNE"] = ",".join(
+        x for x in (os.environ.get("KANO_TUNE", ""), "timing=1") if x)
+    import torch  # noqa: F401  (HIP runtime first, as the bench does)
+    from kano import k8s
+    from kano._engine import DeviceBuild
+    from kano._intern import intern
+    for n in args.pods:
+        pods, pols, nss = cluster(n)
+        t = time.perf_counter()
+        c = k8s.compile_conformant(pods, pols, nss)
+        t_compile = time.perf_counter() - t
+        t = time.perf_counter()
+        te, ti = intern(c.containers, c.egress), intern(c.containers, c.ingress)
+        t_intern = time.perf_counter() - t
+        keep = c.keep(("TCP", 80))
+        rows = (0, n // args.ranks) if args.ranks > 1 else None
+        best = None
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            eg, ing = DeviceBuild(te, build=False), DeviceBuild(ti, build=False)
+            tu = time.perf_counter()
+            eg.build_classes()
+            ing.build_classes()
+            t1 = time.perf_counter()
+            out = DeviceBuild.empty(n, rows=rows)
+            out.k8s_conn_from(eg, ing, True, *keep, form=args.conn_form)   # a port query first
+            dev_port = out.k8s_conn_time()
+            t2 = time.perf_counter()
+            info = out.k8s_conn_from(eg, ing, True, form=args.conn_form)
+            t3 = time.perf_counter()
+            dev = out.k8s_conn_time()
+            r = (t1 - t0, t3 - t2, tu - t0, dev, dev_port)
+            best = r if best is None or r[3] < best[3] else best
+            ie, ii = eg.info(), ing.info()
+            del eg, ing
+        W = (n + 63) // 64
+        nbytes = n * n / 8 / args.ranks
+        from kano import algorithm as alg
+        em = k8s._wrap(out, n)
+        print(json.dumps({
+            "workload": "k8s.connectivity (conformant reading), synthetic K8s cluster",
+            "form": args.conn_form,
+            "pods": n, "namespaces": len(nss), "policies": len(pols),
+            "egress_entries": len(c.egress), "ingress_entries": len(c.ingress),
+            "egress_classes": [ie["U"], ie["UA"]], "ingress_classes": [ii["U"], ii["UA"]],
+            "host_compile_s": round(t_compile, 3), "host_intern_s": round(t_intern, 3),
+            "builds_ms": round(best[0] * 1e3, 3), "of_which_upload_ms": round(best[2] * 1e3, 3),
+            "conn_ms": round(best[1] * 1e3, 3), "conn_device_ms": round(best[3], 4),
+            "conn_port_device_ms": round(best[4], 4),
+            "write_fraction_of_hbm_spec": round(nbytes / (best[3] * 1e-3) / HBM_SPEC, 4)
+            if best[3] > 0 else None,
+            "egress_isolated": info["egress_isolated"],
+            "ingress_isolated": info["ingress_isolated"],
+            "matrix_bytes": 8 * n * W, "ranks": args.ranks, "rows": n // args.ranks,
+            "all_isolated": len(alg.all_isolated(em)) if args.ranks == 1 else None}),
+            flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--conn", action="store_true",
+                    help="the conformant reading (kano.k8s.connectivity) instead of kubesv's edge")
+    ap.add_argument("--conn-form", default="auto", choices=["auto", "direct", "stream"],
+                    help="--conn: how kano_k8s_conn writes the rows")
     ap.add_argument("--pods", type=int, nargs="+", default=[10000, 100000])
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--form", default="classes", choices=["classes", "pods"])
@@ -61,6 +133,8 @@ def main():
     ap.add_argument("--ranks", type=int, default=1,
                     help="time rank 0's row shard of an N-rank split (the edge rows [0, n/N))")
     args = ap.parse_args()
+    if args.conn:
+        return conn(args)
     import torch  # noqa: F401  (HIP runtime first, as the bench does)
     from kano import k8s
     from kano._engine import DeviceBuild
