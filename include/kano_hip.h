@@ -506,6 +506,47 @@ int kano_hop_pairs_fetch(kano_ctx* ctx, int32_t* nodes /* total */);
  * KANO_TUNE=timing=1, else 0. */
 int kano_hops_time(kano_ctx* ctx, float* ms);
 
+/* reverse_matrix / reach_zones: the matrix read by columns, and the pods that
+ * can all reach each other.
+ * kano_reverse: dst[j][i] = src[i][j] for i, j < n, the bit transpose of the
+ * whole matrix on the device.  Bits at positions >= n of a source row's last
+ * word (kano_put_rows copies them unmasked) are no edges; every destination
+ * row's tail bits are written as zero.  dst is a context of the same n on the
+ * same device holding every row (e.g. a context with no policies); afterwards
+ * it is an edited matrix, as after kano_copy_matrix, that every query and
+ * check of this header reads: row t of it is the set of pods that reach t.
+ * src is only read (its matrix, class tables and stored check results are
+ * unchanged); its pending work is waited for first, as for kano_hops /
+ * kano_group_counts, and a call between pipelined kano_verify steps leaves
+ * the next step's results unchanged.  A block moves a tile of 512 source rows
+ * by 8 source words through LDS, whole 64-byte segments on both sides.
+ * info[2] (nullable) = the bits set in the result, the tiles launched.
+ * kano_zones: for two whole matrices A (a) and B (b) of the same n on one
+ * device (a == b allowed), over the bits below n,
+ *   label[i]   = min({i} u {j : A[i,j] = 1 and B[i,j] = 1})
+ *   fan_out[i] = popcount(A[i]), fan_in[i] = popcount(B[i]), cyclic[i] = A[i,i]
+ *   info[2] (nullable) = the distinct labels, the pods with label[i] != i.
+ * With A the transitive closure of M (kano_path, hops = 0) and B its reverse,
+ * label[i] is the smallest member of i's strongly connected component,
+ * fan_out / fan_in the pods i eventually reaches / that eventually reach i,
+ * and cyclic whether i lies on a cycle.  fan_out, fan_in and cyclic may be
+ * NULL; with all three NULL a row stops at its first common bit.  Exact
+ * integers.  Both matrices are only read; pending work of both is waited for.
+ * -EINVAL: a NULL context, src == dst (kano_reverse), a NULL label, matrices
+ * of different n, contexts on two devices, either context holding only a row
+ * shard; -ENOMEM (with a message): a device buffer could not be allocated.
+ * Errors are reported on dst (kano_reverse) and on a (kano_zones).  n == 0
+ * returns 0 before any launch.  Both contexts stay usable after every error. */
+int kano_reverse(kano_ctx* src, kano_ctx* dst, int64_t* info /* 2, or NULL */);
+int kano_zones(kano_ctx* a, kano_ctx* b, int32_t* label /* n */,
+               int32_t* fan_out /* n, or NULL */, int32_t* fan_in /* n, or NULL */,
+               uint8_t* cyclic /* n, or NULL */, int64_t* info /* 2, or NULL */);
+/* The last kano_reverse's device time on its destination (fill and kernel) and
+ * the last kano_zones' on its first context (the kernel), without the copies,
+ * in ms; recorded under KANO_TUNE=timing=1, else 0. */
+int kano_reverse_time(kano_ctx* ctx, float* ms);
+int kano_zones_time(kano_ctx* ctx, float* ms);
+
 /* check_intents: what the cluster is supposed to do, checked against the
  * matrix.  Intent k is a source set src[k] and a destination set dst[k] (W
  * words each, bit j of a set in word j >> 6 at position j & 63, the sets free

@@ -320,6 +320,12 @@ struct kano_ctx {
   // k8s.connectivity (kano_k8s_conn, in the destination context): the device
   // buffers are the call's own; only the time stays
   float conn_ms = 0.f;        // timing=1: the last kano_k8s_conn's fills + kernels
+  // reverse_matrix / reach_zones (kano_reverse, in the destination context;
+  // kano_zones, in the first): the device buffers are the call's own; only
+  // the times stay
+  float reverse_ms = 0.f;     // timing=1: the last kano_reverse's fill + kernel
+  float zones_ms = 0.f;       // timing=1: the last kano_zones' kernel
+  int reverse_tile = 0;       // revtile: k_reverse_tile's form, 0 8 x 8 loads ahead, 1 8 x 8 a row group at a time, 2 16 x 8
   // policy_shadow count-only (kano_verify with shadow_cap < 0): the grouped
   // count (k_shg_*) instead of the pair-by-pair flags
   bool vs_count_only = false;

@@ -13,6 +13,7 @@
 #include "kano_intents.hpp"
 #include "kano_ports.hpp"
 #include "kano_verdict.hpp"
+#include "kano_zones.hpp"
 
 using namespace kano_eng;
 
@@ -2308,6 +2309,143 @@ int kano_k8s_isolated(kano_ctx* ctx, uint8_t* out) {
 int kano_k8s_conn_time(kano_ctx* ctx, float* ms) {
   if (!ctx || !ms) return -EINVAL;
   *ms = ctx->conn_ms;
+  return 0;
+}
+
+}  // extern "C"
+
+// ===========================================================================
+// reverse_matrix / reach_zones: the matrix read by columns (k_reverse_tile)
+// and the per-row pass over a matrix and its reverse (k_zone_rows;
+// kano_zones.hpp).
+// ===========================================================================
+namespace {
+
+// the shared preamble of two whole matrices of the same n on one device:
+// both present, `other`'s pending work complete; the work then runs on ctx's
+// stream and errors are reported on ctx
+int zones_prepare(kano_ctx* other, kano_ctx* ctx, const char* what) {
+  for (const kano_ctx* c : {other, ctx})
+    if (c->r0 != 0 || c->r1 != c->n)
+      return fail(ctx, -EINVAL, std::string(what) + ": a context holds rows [" +
+                                    std::to_string(c->r0) + ", " + std::to_string(c->r1) +
+                                    ") of " + std::to_string(c->n) + ": it needs every row");
+  KTRY(diff_prepare(other, ctx, what));
+  return sync(ctx);
+}
+
+template <int A, int B, bool AHEAD>
+int reverse_launch(kano_ctx* ctx, const u64* S, i64 ldS, u64* D, i64 ldD, i64 n, i64 W,
+                   unsigned long long* bits, i64* tiles) {
+  const i64 gx = (W + B - 1) / B, gy = (n + 64 * A - 1) / (64 * A);
+  if (gx * gy > 0x7fffffff)
+    return fail(ctx, -ENOTSUP, "kano_reverse: " + std::to_string(gx * gy) + " tiles in one launch");
+  hipLaunchKernelGGL((k_reverse_tile<A, B, AHEAD>), dim3((unsigned)(gx * gy)), dim3(TPB), 0, ctx->stream,
+                     S, ldS, D, ldD, n, W, gx, bits);
+  KLAUNCH();
+  *tiles = gx * gy;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kano_reverse(kano_ctx* src, kano_ctx* dst, int64_t* info) {
+  if (!src || !dst) return -EINVAL;
+  kano_ctx* ctx = dst;
+  if (info) info[0] = info[1] = 0;
+  if (src == dst)
+    return fail(dst, -EINVAL, "kano_reverse: the destination must be another context");
+  KTRY(zones_prepare(src, dst, "kano_reverse"));
+  dst->reverse_ms = 0.f;
+  const i64 n = dst->n, W = dst->W;
+  if (n == 0 || W == 0) return 0;
+  unsigned long long bits = 0;
+  i64 tiles = 0;
+  DBuf cnt;
+  auto run = [&]() -> int {
+    KTRY(dalloc(ctx, cnt, sizeof(unsigned long long)));
+    // timing=1: the call's device time (the fill and the kernel, no copy)
+    EventPair<> tev;
+    if (dst->stage_timing) KTRY(tev.start(ctx));
+    KCHK(hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long), ctx->stream));
+    const u64* S = P_<u64>(src->M);
+    u64* D = P_<u64>(dst->M);
+    unsigned long long* c = P_<unsigned long long>(cnt);
+    if (dst->reverse_tile == 1)        // (the forms measured against the default: DESIGN.md)
+      KTRY((reverse_launch<8, 8, false>(ctx, S, src->ldM, D, dst->ldM, n, W, c, &tiles)));
+    else if (dst->reverse_tile == 2)
+      KTRY((reverse_launch<16, 8, true>(ctx, S, src->ldM, D, dst->ldM, n, W, c, &tiles)));
+    else
+      KTRY((reverse_launch<8, 8, true>(ctx, S, src->ldM, D, dst->ldM, n, W, c, &tiles)));
+    KTRY(tev.stop(ctx, &dst->reverse_ms));
+    KCHK(hipMemcpyAsync(&bits, cnt.p, sizeof(bits), hipMemcpyDeviceToHost, ctx->stream));
+    return sync(ctx);
+  };
+  const int rc = run();
+  derived_end(dst, {&cnt}, rc);
+  if (rc) return rc;
+  if (info) {
+    info[0] = (int64_t)bits;
+    info[1] = tiles;
+  }
+  return 0;
+}
+
+int kano_reverse_time(kano_ctx* ctx, float* ms) {
+  if (!ctx || !ms) return -EINVAL;
+  *ms = ctx->reverse_ms;
+  return 0;
+}
+
+int kano_zones(kano_ctx* a, kano_ctx* b, int32_t* label, int32_t* fan_out, int32_t* fan_in,
+               uint8_t* cyclic, int64_t* info) {
+  if (!a || !b) return -EINVAL;
+  kano_ctx* ctx = a;
+  if (info) info[0] = info[1] = 0;
+  if (!label) return fail(a, -EINVAL, "kano_zones: label is NULL");
+  KTRY(zones_prepare(b, a, "kano_zones"));
+  a->zones_ms = 0.f;
+  const i64 n = a->n, W = a->W;
+  if (n == 0 || W == 0) return 0;
+  const bool counts = fan_out || fan_in || cyclic;
+  // the call's own buffer: [label | fan_out | fan_in] int32, then cyclic
+  DBuf out;
+  auto run = [&]() -> int {
+    KTRY(dalloc(ctx, out, sizeof(int32_t) * 3 * (size_t)n + (size_t)n));
+    int32_t* lab = P_<int32_t>(out);
+    uint8_t* cyc = reinterpret_cast<uint8_t*>(lab + 3 * n);
+    // timing=1: the call's device time (the kernel, no copy)
+    EventPair<> tev;
+    if (a->stage_timing) KTRY(tev.start(ctx));
+    hipLaunchKernelGGL(k_zone_rows, dim3(nblk(n, TPB / 64)), dim3(TPB), 0, ctx->stream,
+                       (const u64*)P_<u64>(a->M), a->ldM, (const u64*)P_<u64>(b->M), b->ldM, n, W,
+                       counts ? 1 : 0, lab, lab + n, lab + 2 * n, cyc);
+    KLAUNCH();
+    KTRY(tev.stop(ctx, &a->zones_ms));
+    const size_t nb = sizeof(int32_t) * (size_t)n;
+    KCHK(hipMemcpyAsync(label, lab, nb, hipMemcpyDeviceToHost, ctx->stream));
+    if (fan_out) KCHK(hipMemcpyAsync(fan_out, lab + n, nb, hipMemcpyDeviceToHost, ctx->stream));
+    if (fan_in) KCHK(hipMemcpyAsync(fan_in, lab + 2 * n, nb, hipMemcpyDeviceToHost, ctx->stream));
+    if (cyclic) KCHK(hipMemcpyAsync(cyclic, cyc, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    return sync(ctx);
+  };
+  const int rc = run();
+  free_temps(ctx, rc, {&out});
+  if (rc) return rc;
+  if (info) {
+    std::vector<int32_t> s(label, label + n);
+    std::sort(s.begin(), s.end());
+    info[0] = (int64_t)(std::unique(s.begin(), s.end()) - s.begin());
+    for (i64 i = 0; i < n; ++i) info[1] += label[i] != (int32_t)i;
+  }
+  return 0;
+}
+
+int kano_zones_time(kano_ctx* ctx, float* ms) {
+  if (!ctx || !ms) return -EINVAL;
+  *ms = ctx->zones_ms;
   return 0;
 }
 

@@ -2353,6 +2353,7 @@ int kano_create(int device, kano_ctx** out) {
         if (k == "dgrid" && v >= 0) ctx->diff_grid = v;
         if (k == "ggrid" && v >= 0) ctx->group_grid = v;
         if (k == "gbatch" && v >= 0) ctx->group_batches = v;
+        if (k == "revtile" && v >= 0 && v <= 2) ctx->reverse_tile = v;
         if (k == "shr" && (v == 1 || v == 2 || v == 4 || v == 8)) ctx->shadow_r = v;
         if (k == "rcu" && v >= 0 && v <= 28 && (v < 4 || v % 4 == 0)) ctx->rows_cu_off = v;
         if (k == "rcubytes" && v >= 0) ctx->rows_cu_bytes = (i64)v << 30;

@@ -927,6 +927,49 @@ class DeviceBuild:
         self._chk(self.lib.kano_hops_time(self.ctx, byref(ms)), "kano_hops_time")
         return float(ms.value)
 
+    # -- reverse_matrix / reach_zones (kano_reverse / kano_zones) -----------
+    def reverse_into(self, dst: "DeviceBuild") -> dict:
+        """``dst``'s matrix := this context's matrix transposed, on the device
+        (kano_reverse): row t of ``dst`` is the set of pods that reach t.
+        Both contexts hold every row of matrices of the same n.  Returns
+        ``bits`` (set in the result) and ``tiles`` (launched)."""
+        info = np.zeros(2, dtype=np.int64)
+        # (errors are reported on the destination)
+        nat.check(dst.ctx, self.lib.kano_reverse(self.ctx, dst.ctx, _ptr(info)), "kano_reverse")
+        return dict(bits=int(info[0]), tiles=int(info[1]))
+
+    def reverse_time(self) -> float:
+        """The last reverse_into's device time with this context as ``dst``
+        (ms; KANO_TUNE=timing=1)."""
+        ms = ctypes.c_float(0.0)
+        self._chk(self.lib.kano_reverse_time(self.ctx, byref(ms)), "kano_reverse_time")
+        return float(ms.value)
+
+    def zones(self, other: "DeviceBuild", counts: bool = True) -> dict:
+        """Per pod i over this context's matrix A and ``other``'s B (the same
+        n, every row): ``label`` = min({i} | {j : A[i,j] and B[i,j]}) (int32)
+        and, with ``counts``, ``fan_out`` = popcount(A[i]), ``fan_in`` =
+        popcount(B[i]) (int32) and ``cyclic`` = A[i,i] (bool); else those are
+        None and a row stops at its first common bit.  ``zones`` is the number
+        of distinct labels, ``moved`` the pods with label[i] != i."""
+        n = self.info()["N"]
+        label = np.empty(n, dtype=np.int32)
+        fo = np.empty(n, dtype=np.int32) if counts else None
+        fi = np.empty(n, dtype=np.int32) if counts else None
+        cy = np.empty(n, dtype=np.uint8) if counts else None
+        info = np.zeros(2, dtype=np.int64)
+        self._chk(self.lib.kano_zones(self.ctx, other.ctx, _ptr(label), _ptr(fo), _ptr(fi),
+                                      _ptr(cy), _ptr(info)), "kano_zones")
+        return dict(label=label, fan_out=fo, fan_in=fi,
+                    cyclic=cy.astype(bool) if counts else None,
+                    zones=int(info[0]), moved=int(info[1]))
+
+    def zones_time(self) -> float:
+        """The last zones' device time (ms; KANO_TUNE=timing=1)."""
+        ms = ctypes.c_float(0.0)
+        self._chk(self.lib.kano_zones_time(self.ctx, byref(ms)), "kano_zones_time")
+        return float(ms.value)
+
     # -- check_intents (kano_intents / kano_intent_pairs) -------------------
     INTENT_ALLOW, INTENT_SELF = 1, 2     # flag bits
     INTENT_RUN_ROWS = 16                 # csrc/kano_intents.hpp INTENT_R: rows of a work item at least

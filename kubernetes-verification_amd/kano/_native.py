@@ -87,6 +87,10 @@ SIGNATURES = {
                                POINTER(c_int64)]),
     "kano_hop_pairs_fetch": (c_int, [c_void_p, c_void_p]),
     "kano_hops_time": (c_int, [c_void_p, POINTER(c_float)]),
+    "kano_reverse": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "kano_reverse_time": (c_int, [c_void_p, POINTER(c_float)]),
+    "kano_zones": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "kano_zones_time": (c_int, [c_void_p, POINTER(c_float)]),
     "kano_intents": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_void_p]),
     "kano_intent_pairs": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int64,

@@ -709,6 +709,141 @@ def path_witness(matrix: ReachabilityMatrix, i: int, j: int, max_hops: int = 0) 
 
 
 # ---------------------------------------------------------------------------
+# Who reaches a pod, and which pods can all reach each other.  Not part of
+# kano_py's algorithm.py.  Every query above starts at a source row;
+# reverse_matrix gives the matrix read by columns as a matrix of its own
+# (R[t, s] = M[s, t], the bit transpose on the device: kano_reverse), so the
+# same queries answer from the destination's side.  reach_zones turns the
+# closure's bits into lateral-movement zones: with C = transitive_closure(M),
+# "j = i, or C[i, j] and C[j, i]" is an equivalence relation whose classes are
+# the strongly connected components of the reachability graph, and
+#   label[i]   = the smallest pod of i's zone,
+#   fan_out[i] = popcount(C[i]): the pods i eventually reaches,
+#   fan_in[i]  = popcount(C[:, i]): the pods that eventually reach i,
+#   cyclic[i]  = C[i, i]: i lies on a cycle
+# from one pass over C and its reverse (kano_zones).  zone_graph counts M's
+# own edges between the zones; between different zones it is acyclic.  Whole
+# matrices on one device only: a row shard raises.  reach_zones holds M, C and
+# the reverse of C at once (three n x n bit matrices); the closure of an
+# edited matrix takes kano_path's pod-level form.  Not covered: row shards,
+# groups of several members, a closure-free forward / backward search,
+# incremental maintenance of the zones.
+
+class Zones(NamedTuple):
+    label: np.ndarray          # int32 (n): the smallest pod of the pod's zone
+    fan_out: np.ndarray        # int32 (n): pods it eventually reaches
+    fan_in: np.ndarray         # int32 (n): pods that eventually reach it
+    cyclic: np.ndarray         # bool (n): it lies on a cycle
+
+    def reps(self) -> np.ndarray:
+        """The distinct labels, ascending: one representative per zone."""
+        return np.unique(np.asarray(self.label, dtype=np.int32))
+
+    def sizes(self) -> np.ndarray:
+        """Pods per zone, aligned with ``reps()``."""
+        return np.unique(np.asarray(self.label), return_counts=True)[1].astype(np.int64)
+
+    def members(self, z: int) -> List[int]:
+        """The pods of the zone whose representative is ``z``, ascending."""
+        return np.flatnonzero(np.asarray(self.label) == int(z)).tolist()
+
+    def nontrivial(self, min_size: int = 2) -> np.ndarray:
+        """The representatives of the zones with at least ``min_size`` pods."""
+        return self.reps()[self.sizes() >= int(min_size)]
+
+    def index(self, min_size: int = 1) -> np.ndarray:
+        """A dense zone id per pod (int32), in ``reps()`` order over the zones
+        with at least ``min_size`` pods; -1 for the pods of smaller zones."""
+        reps, inv, cnt = np.unique(np.asarray(self.label), return_inverse=True,
+                                   return_counts=True)
+        keep = cnt >= int(min_size)
+        dense = np.where(keep, np.cumsum(keep) - 1, -1).astype(np.int32)
+        return dense[inv.reshape(-1)]
+
+
+class ZoneGraph(NamedTuple):
+    reps: np.ndarray           # int32: the zones' representatives, ascending
+    counts: np.ndarray         # int64 (Z, Z): M's edges from zone a into zone b
+
+
+def reverse_matrix(matrix: ReachabilityMatrix) -> ReachabilityMatrix:
+    """The matrix read by columns, as a new rows-only matrix on the device:
+    row t of the result is the set of pods that reach t.  So
+    ``hop_levels(reverse_matrix(m), t)`` is who reaches t and in how many
+    hops, ``group_fanout`` on it is the per-pod fan-in by group, and
+    ``check_intents`` on it reads the intents from the destination's side.
+    Needs the whole matrix on one device (a row shard raises)."""
+    from ._engine import DeviceBuild
+    from .multi import MultiBuild
+    src = _engine(matrix, whole=True)
+    n = matrix.container_size
+    if isinstance(src, MultiBuild):
+        src._zones_member("reverse_matrix")
+    out = ReachabilityMatrix.__new__(ReachabilityMatrix)
+    out.container_size = n
+    out._engine = (MultiBuild.empty(n, src.G, devices=src.devices)
+                   if isinstance(src, MultiBuild) else DeviceBuild.empty(n, device=src.device))
+    out._containers = None
+    out._policies = None
+    out._ncontainers = n
+    out._lists = None
+    try:
+        out.reverse_info = src.reverse_into(out._engine)
+    except BaseException:
+        out._engine.close()
+        raise
+    return out
+
+
+def reach_zones(matrix: ReachabilityMatrix,
+                closure: Optional[ReachabilityMatrix] = None) -> Zones:
+    """The lateral-movement zones of ``matrix`` (see Zones): the strongly
+    connected components of its reachability graph with per-pod eventual
+    fan-out and fan-in.  ``closure`` is ``transitive_closure(matrix)`` when
+    the caller already holds it; else it is computed here.  Every temporary
+    matrix the call creates is closed before it returns."""
+    _engine(matrix, whole=True)
+    n = matrix.container_size
+    if closure is not None and closure.container_size != n:
+        raise ValueError("the closure is of another size than the matrix")
+    if n == 0:
+        e = np.zeros(0, np.int32)
+        return Zones(e, e.copy(), e.copy(), np.zeros(0, bool))
+    made = []
+    try:
+        if closure is None:
+            closure = transitive_closure(matrix)
+            made.append(closure)
+        rev = reverse_matrix(closure)
+        made.append(rev)
+        r = _engine(closure, whole=True).zones(rev._engine)
+    finally:
+        for m in made:
+            m._engine.close()
+    return Zones(r["label"], r["fan_out"], r["fan_in"], r["cyclic"])
+
+
+def zone_graph(matrix: ReachabilityMatrix, zones: Zones, min_size: int = 1) -> ZoneGraph:
+    """The graph between the zones of at least ``min_size`` pods on the
+    matrix's own edges: ``counts[a, b]`` is the number of pairs (i, j) with
+    M[i, j] = 1, i in zone ``reps[a]`` and j in zone ``reps[b]`` (the
+    diagonal: the edges inside a zone).  Off the diagonal the graph is
+    acyclic.  Counted on the device (kano_group_counts)."""
+    eng = _engine(matrix, whole=True)
+    n = matrix.container_size
+    if len(zones.label) != n:
+        raise ValueError("zones of another size than the matrix")
+    reps = zones.nontrivial(min_size).astype(np.int32)
+    Z = len(reps)
+    if Z * Z > 1 << 27:
+        raise ValueError(f"{Z} zones make {Z * Z} counts, beyond 2^27: raise min_size")
+    if Z == 0:
+        return ZoneGraph(reps, np.zeros((0, 0), np.int64))
+    idx = zones.index(min_size)
+    return ZoneGraph(reps, eng.group_counts(idx, idx, Z, Z)["counts"])
+
+
+# ---------------------------------------------------------------------------
 # What the cluster is supposed to do.  Not part of kano_py's algorithm.py.
 # The checks above are fixed questions; an Intent (kano/intent.py) is the
 # operator's own: "no src pod may reach a dst pod" (deny) or "every src pod

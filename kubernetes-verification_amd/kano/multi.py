@@ -597,6 +597,29 @@ class MultiBuild:
     def hops_time(self) -> float:
         return self._hops_member().hops_time()
 
+    # -- reverse_matrix / reach_zones ---------------------------------------------
+    def _zones_member(self, what: str) -> DeviceBuild:
+        """A column of the matrix crosses every row shard: the transpose and
+        the zone pass need the whole matrix on one device."""
+        if len(self.members) != 1:
+            raise ValueError(f"{what} needs the whole matrix on one device: this group "
+                             f"holds it in {len(self.members)} row shards")
+        return self.members[0]
+
+    def reverse_into(self, dst) -> dict:
+        d = dst._zones_member("reverse_into") if isinstance(dst, MultiBuild) else dst
+        return self._zones_member("reverse_into").reverse_into(d)
+
+    def reverse_time(self) -> float:
+        return self._zones_member("reverse_time").reverse_time()
+
+    def zones(self, other, counts: bool = True) -> dict:
+        o = other._zones_member("zones") if isinstance(other, MultiBuild) else other
+        return self._zones_member("zones").zones(o, counts=counts)
+
+    def zones_time(self) -> float:
+        return self._zones_member("zones_time").zones_time()
+
     # -- check_intents --------------------------------------------------------------
     INTENT_ALLOW, INTENT_SELF = DeviceBuild.INTENT_ALLOW, DeviceBuild.INTENT_SELF
 
