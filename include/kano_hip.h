@@ -896,8 +896,43 @@ int kano_k8s_conn(kano_ctx* eg, kano_ctx* in, kano_ctx* dst, int flags,
                   int64_t nids_i, const uint8_t* keep_i /* nids_i, nullable: all */,
                   int64_t* info /* 4, nullable */);
 int kano_k8s_isolated(kano_ctx* ctx, uint8_t* out /* n */);
-/* KANO_TUNE timing=1: the last kano_k8s_conn's device time in ms on its
- * destination (the fills and the kernels, no copies), else 0. */
+/* k8s.connectivity with AdminNetworkPolicy tiers (policy.networking.k8s.io/
+ * v1alpha1: Allow / Deny / Pass above the NetworkPolicies, the
+ * BaselineAdminNetworkPolicy below them).  The host compiles the rules of all
+ * three kinds into the same two builds (an entry selects a rule's subject and
+ * allows one peer) and gives every engine id a code = level * 4 + action:
+ * action 0 allow, 1 deny, 2 pass, 3 isolates only; 0xffffffff: the entry is
+ * dropped (its rule does not count on the queried port).  A level is one rule:
+ * the levels below np_level are the admin rules in evaluation order, np_level
+ * is the NetworkPolicy tier (action 0, or 3 for an entry that selects without
+ * allowing: a policy without rules, or a rule the port drops), the levels above
+ * it the baseline's rules in order.  Per direction (egress: subject x = src,
+ * peer y = dst, build eg; ingress: x = dst, y = src, build in) over the live
+ * entries selecting x and allowing y:
+ *   the lowest admin level decides -- allow, deny -- or passes; where none
+ *   matches or it passes: x selected by some live entry at np_level (isolated)
+ *   ? some allow entry at np_level matches : the lowest baseline level
+ *   decides, and where none matches the pair is allowed.
+ * (Several actions on one level resolve allow, deny, pass in that order.)
+ *   allowed[s][d] = (s == d and flags & KANO_K8S_CONN_SELF) | eg(s, d) & in(d, s)
+ * Sources, destination, flags, forms, limits and error reporting as for
+ * kano_k8s_conn; additionally -EINVAL for NULL codes with nids > 0, an
+ * np_level of 2^30 or more (so no level reaches 2^30) and a live code that
+ * passes at or above np_level, only isolates off np_level or denies at
+ * np_level.  iso_e / iso_i (nullable, n bytes each): 1 iff the pod is selected
+ * by a live entry at np_level (some NetworkPolicy of that type selects it);
+ * zeros for a side without classes.  info (nullable) = [egress-isolated pods,
+ * ingress-isolated pods, live egress codes, live ingress codes]; the first two
+ * stay 0 when nothing is launched (n == 0).  A destination holding no rows
+ * still gets the flags and counts.  The device buffers (codes, ordered copies,
+ * class-level rows, flags) are the call's own, freed on return.  Exact bits. */
+int kano_k8s_conn_tiers(kano_ctx* eg, kano_ctx* in, kano_ctx* dst, int flags,
+                        int64_t nids_e, const uint32_t* code_e /* nids_e */, uint32_t np_level_e,
+                        int64_t nids_i, const uint32_t* code_i /* nids_i */, uint32_t np_level_i,
+                        uint8_t* iso_e /* n, nullable */, uint8_t* iso_i /* n, nullable */,
+                        int64_t* info /* 4, nullable */);
+/* KANO_TUNE timing=1: the last kano_k8s_conn's or kano_k8s_conn_tiers' device
+ * time in ms on its destination (the fills and the kernels, no copies), else 0. */
 int kano_k8s_conn_time(kano_ctx* ctx, float* ms);
 
 /* kano_build without the matrix write (model.py:125-165 up to the class-level

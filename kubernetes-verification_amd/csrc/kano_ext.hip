@@ -8,6 +8,7 @@
 #include "kano_inc.hpp"
 #include "kano_k8s.hpp"
 #include "kano_k8s_conn.hpp"
+#include "kano_k8s_tiers.hpp"
 #include "kano_path.hpp"
 #include "kano_hops.hpp"
 #include "kano_intents.hpp"
@@ -2120,47 +2121,142 @@ int conn_source(kano_ctx* s, kano_ctx* err_ctx, const char* what) {
 // without policies a build has no classes: that direction constrains nothing
 bool conn_classes(const kano_ctx* s) { return s->P > 0 && s->rc.U > 0 && s->cc.U > 0; }
 
+// The write of dst's held rows from the two class-level tables Re (egress) and
+// Ri (ingress; transposed here), shared by kano_k8s_conn and
+// kano_k8s_conn_tiers: alloc takes the call's buffers (before the timed
+// stretch) and picks the form, launch enqueues the transpose and the rows.
+struct ConnWrite {
+  DBuf ti, xr;
+  bool stream = false;
+
+  int alloc(kano_ctx* eg, kano_ctx* in, kano_ctx* dst, int flags, bool hasE, bool hasI) {
+    kano_ctx* ctx = dst;
+    const i64 Ue = eg->rc.U, Ui = in->rc.U, Xi = in->cc.U, KWi = (Ui + 63) / 64;
+    const i64 rl = rows_local(dst);
+    if (hasI) KTRY(dalloc(ctx, ti, sizeof(u64) * (size_t)(Xi * KWi)));
+    // the streamed form when the class rows are few beside the held rows (as
+    // kano_k8s_edge picks it), or as the flags force
+    const i64 Us = (hasE ? Ue : 0) + (hasI ? Xi : 0);
+    // (its class-row expansions' grids hold at most 65535 * 64 class rows a
+    // table: beyond that the direct form, whatever the flags say)
+    const i64 xmax = (i64)65535 * K8S_XR;
+    stream = Us > 0 && !(flags & KANO_K8S_CONN_DIRECT) && (!hasE || Ue <= xmax) &&
+             (!hasI || Xi <= xmax) &&
+             ((flags & KANO_K8S_CONN_STREAM) || Us <= std::max<i64>(rl / 2, 1));
+    if (stream) KTRY(dalloc(ctx, xr, sizeof(u64) * (size_t)(Us * dst->ldM)));
+    return 0;
+  }
+
+  int launch(kano_ctx* eg, kano_ctx* in, kano_ctx* dst, int flags, bool hasE, bool hasI,
+             const u64* re, const u64* ri) {
+    kano_ctx* ctx = dst;
+    const i64 n = dst->n, W = dst->W, ldM = dst->ldM, r0 = dst->r0, rl = rows_local(dst);
+    const i64 Ue = eg->rc.U, ldCe = eg->ldC, Ui = in->rc.U, Xi = in->cc.U, ldCi = in->ldC;
+    const i64 KWi = (Ui + 63) / 64;
+    if (hasI) {
+      const i64 CGi = ((Xi + 63) / 64 + 15) / 16;
+      hipLaunchKernelGGL(k_k8s_transpose, dim3(nblk(KWi * CGi, TPB / 64)), dim3(TPB), 0,
+                         ctx->stream, ri, ldCi, Ui, KWi, CGi, Xi, P_<u64>(ti), KWi);
+      KLAUNCH();
+    }
+    const int self = (flags & KANO_K8S_CONN_SELF) ? 1 : 0;
+    const int32_t* rce = P_<int32_t>(eg->rc.cls);
+    const int32_t* cce = P_<int32_t>(eg->cc.cls);
+    const int32_t* cci = P_<int32_t>(in->cc.cls);
+    const int32_t* rci = P_<int32_t>(in->rc.cls);
+    if (stream) {
+      // the class rows of both tables expanded to pod words once (row r is
+      // class r, the other table absent, no diagonal), then streamed to the
+      // held rows (kernels picked through a pointer are launched by handle:
+      // see launch_marked)
+      u64* XE = hasE ? P_<u64>(xr) : nullptr;
+      u64* XT = hasI ? P_<u64>(xr) + (hasE ? Ue : 0) * ldM : nullptr;
+      const int32_t* const none = nullptr;
+      if (hasE) {
+        auto CONN_EXPAND = ldCe <= CONN_STAGE_W ? k_conn_expand<true> : k_conn_expand<false>;
+        hipExtLaunchKernelGGL(CONN_EXPAND, dim3(nblk(ldM, K8S_XW), nblk(Ue, K8S_XR)), dim3(TPB), 0,
+                              ctx->stream, nullptr, nullptr, 0, re, ldCe, none, cce,
+                              (const u64*)nullptr, (i64)0, none, none, 0, (i64)0, Ue, n, W, XE,
+                              ldM);
+        KLAUNCH();
+      }
+      if (hasI) {
+        auto CONN_EXPAND = KWi <= CONN_STAGE_W ? k_conn_expand<true> : k_conn_expand<false>;
+        hipExtLaunchKernelGGL(CONN_EXPAND, dim3(nblk(ldM, K8S_XW), nblk(Xi, K8S_XR)), dim3(TPB), 0,
+                              ctx->stream, nullptr, nullptr, 0, (const u64*)nullptr, (i64)0, none,
+                              none, (const u64*)P_<u64>(ti), KWi, none, rci, 0, (i64)0, Xi, n, W,
+                              XT, ldM);
+        KLAUNCH();
+      }
+      hipLaunchKernelGGL(k_conn_rows, dim3(nblk(rl * (ldM / 2))), dim3(TPB), 0, ctx->stream,
+                         (const u64*)XE, rce, (const u64*)XT, cci, self, r0, rl, ldM,
+                         P_<u64>(dst->M));
+      KLAUNCH();
+    } else {
+      // class rows of <= CONN_STAGE_W words together are staged in LDS by the expansion
+      const bool stage = (hasE ? ldCe : 0) + (hasI ? KWi : 0) <= CONN_STAGE_W;
+      auto CONN_EXPAND = stage ? k_conn_expand<true> : k_conn_expand<false>;
+      hipExtLaunchKernelGGL(CONN_EXPAND, dim3(nblk(ldM, K8S_XW), nblk(rl, K8S_XR)), dim3(TPB), 0,
+                            ctx->stream, nullptr, nullptr, 0, hasE ? re : nullptr, ldCe, rce, cce,
+                            (const u64*)(hasI ? P_<u64>(ti) : nullptr), KWi, cci, rci, self, r0,
+                            rl, n, W, P_<u64>(dst->M), ldM);
+      KLAUNCH();
+    }
+    return 0;
+  }
+};
+
+// The shared preamble of kano_k8s_conn and kano_k8s_conn_tiers: the three
+// contexts checked and ready, the sources' classes complete.  Errors on dst.
+int conn_begin(kano_ctx* eg, kano_ctx* in, kano_ctx* dst, const char* what, i64 nids_e,
+               i64 nids_i) {
+  if (!eg || !in || !dst) return -EINVAL;
+  const std::string w(what);
+  if (dst == eg || dst == in)
+    return fail(dst, -EINVAL, w + ": the destination must be another context");
+  if (eg->device != dst->device || in->device != dst->device)
+    return fail(dst, -EINVAL, w + ": contexts on two devices");
+  kano_ctx* ctx = dst;
+  KCHK(hipSetDevice(dst->device));
+  KTRY(conn_source(eg, dst, what));
+  KTRY(conn_source(in, dst, what));
+  KTRY(ensure_matrix(dst));
+  const i64 n = dst->n, rl = rows_local(dst);
+  if (eg->n != n || in->n != n)
+    return fail(dst, -EINVAL, w + ": the three contexts must hold the same pods");
+  if (nids_e != eg->P || nids_i != in->P)
+    return fail(dst, -EINVAL, w + ": nids = " + std::to_string(nids_e) + " / " +
+                                  std::to_string(nids_i) + ", the sources have " +
+                                  std::to_string(eg->P) + " / " + std::to_string(in->P) +
+                                  " engine ids");
+  if ((rl + K8S_XR - 1) / K8S_XR > 65535)   // (k_conn_expand's grid)
+    return fail(dst, -ENOTSUP, w + ": more than 4,194,240 rows in one context");
+  for (kano_ctx* s : {eg, in}) {
+    const int rc = sync(s);   // the sources' classes are complete
+    if (rc) return fail(dst, rc, w + ": source: " + s->err);
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
 
 int kano_k8s_conn(kano_ctx* eg, kano_ctx* in, kano_ctx* dst, int flags, int64_t nids_e,
                   const uint8_t* keep_e, int64_t nids_i, const uint8_t* keep_i, int64_t* info) {
-  if (!eg || !in || !dst) return -EINVAL;
-  const char* const what = "kano_k8s_conn";
-  if (dst == eg || dst == in)
-    return fail(dst, -EINVAL, "kano_k8s_conn: the destination must be another context");
-  if (eg->device != dst->device || in->device != dst->device)
-    return fail(dst, -EINVAL, "kano_k8s_conn: contexts on two devices");
+  KTRY(conn_begin(eg, in, dst, "kano_k8s_conn", nids_e, nids_i));
   kano_ctx* ctx = dst;
-  KCHK(hipSetDevice(dst->device));
-  KTRY(conn_source(eg, dst, what));
-  KTRY(conn_source(in, dst, what));
-  KTRY(ensure_matrix(dst));
-  const i64 n = dst->n, W = dst->W, ldM = dst->ldM, r0 = dst->r0, rl = rows_local(dst);
-  if (eg->n != n || in->n != n)
-    return fail(dst, -EINVAL, "kano_k8s_conn: the three contexts must hold the same pods");
-  if (nids_e != eg->P || nids_i != in->P)
-    return fail(dst, -EINVAL, "kano_k8s_conn: nids = " + std::to_string(nids_e) + " / " +
-                                  std::to_string(nids_i) + ", the sources have " +
-                                  std::to_string(eg->P) + " / " + std::to_string(in->P) +
-                                  " engine ids");
-  if ((rl + K8S_XR - 1) / K8S_XR > 65535)   // (k_conn_expand's grid)
-    return fail(dst, -ENOTSUP, "kano_k8s_conn: more than 4,194,240 rows in one context");
-  for (kano_ctx* s : {eg, in}) {
-    const int rc = sync(s);   // the sources' classes are complete
-    if (rc) return fail(dst, rc, "kano_k8s_conn: source: " + s->err);
-  }
+  const i64 n = dst->n, rl = rows_local(dst);
   const bool hasE = conn_classes(eg), hasI = conn_classes(in);
   i64 kept[2] = {0, 0};
   for (i64 p = 0; p < nids_e; ++p) kept[0] += keep_e ? keep_e[p] != 0 : 1;
   for (i64 p = 0; p < nids_i; ++p) kept[1] += keep_i ? keep_i[p] != 0 : 1;
   unsigned long long iso[2] = {0, 0};
   dst->conn_ms = 0.f;
-  DBuf ke, ki, re, ri, ti, xr, cnt;
+  DBuf ke, ki, re, ri, cnt;
+  ConnWrite wr;
   auto run = [&]() -> int {
-    const i64 Ue = eg->rc.U, ldCe = eg->ldC, Ui = in->rc.U, Xi = in->cc.U, ldCi = in->ldC;
-    const i64 KWi = (Ui + 63) / 64;
+    const i64 Ue = eg->rc.U, ldCe = eg->ldC, Ui = in->rc.U, ldCi = in->ldC;
     KTRY(dalloc(ctx, cnt, sizeof(unsigned long long) * 2));
     if (hasE) {
       KTRY(dalloc(ctx, re, sizeof(u64) * (size_t)(Ue * ldCe)));
@@ -2171,22 +2267,12 @@ int kano_k8s_conn(kano_ctx* eg, kano_ctx* in, kano_ctx* dst, int flags, int64_t 
     }
     if (hasI) {
       KTRY(dalloc(ctx, ri, sizeof(u64) * (size_t)(Ui * ldCi)));
-      KTRY(dalloc(ctx, ti, sizeof(u64) * (size_t)(Xi * KWi)));
       if (keep_i) {
         KTRY(dalloc(ctx, ki, (size_t)nids_i));
         KCHK(hipMemcpyAsync(ki.p, keep_i, (size_t)nids_i, hipMemcpyHostToDevice, ctx->stream));
       }
     }
-    // the streamed form when the class rows are few beside the held rows (as
-    // kano_k8s_edge picks it), or as the flags force
-    const i64 Us = (hasE ? Ue : 0) + (hasI ? Xi : 0);
-    // (its class-row expansions' grids hold at most 65535 * 64 class rows a
-    // table: beyond that the direct form, whatever the flags say)
-    const i64 xmax = (i64)65535 * K8S_XR;
-    const bool stream = Us > 0 && !(flags & KANO_K8S_CONN_DIRECT) &&
-                        (!hasE || Ue <= xmax) && (!hasI || Xi <= xmax) &&
-                        ((flags & KANO_K8S_CONN_STREAM) || Us <= std::max<i64>(rl / 2, 1));
-    if (stream) KTRY(dalloc(ctx, xr, sizeof(u64) * (size_t)(Us * ldM)));
+    KTRY(wr.alloc(eg, in, dst, flags, hasE, hasI));
     EventPair<> tev;
     if (dst->stage_timing) KTRY(tev.start(ctx));
     KCHK(hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long) * 2, ctx->stream));
@@ -2209,64 +2295,15 @@ int kano_k8s_conn(kano_ctx* eg, kano_ctx* in, kano_ctx* dst, int flags, int64_t 
                          (uint8_t*)nullptr, P_<unsigned long long>(cnt) + side);
       KLAUNCH();
     }
-    if (hasI) {
-      const i64 CGi = ((Xi + 63) / 64 + 15) / 16;
-      hipLaunchKernelGGL(k_k8s_transpose, dim3(nblk(KWi * CGi, TPB / 64)), dim3(TPB), 0,
-                         ctx->stream, (const u64*)P_<u64>(ri), ldCi, Ui, KWi, CGi, Xi, P_<u64>(ti),
-                         KWi);
-      KLAUNCH();
-    }
-    const int self = (flags & KANO_K8S_CONN_SELF) ? 1 : 0;
-    const int32_t* rce = P_<int32_t>(eg->rc.cls);
-    const int32_t* cce = P_<int32_t>(eg->cc.cls);
-    const int32_t* cci = P_<int32_t>(in->cc.cls);
-    const int32_t* rci = P_<int32_t>(in->rc.cls);
-    if (stream) {
-      // the class rows of both tables expanded to pod words once (row r is
-      // class r, the other table absent, no diagonal), then streamed to the
-      // held rows (kernels picked through a pointer are launched by handle:
-      // see launch_marked)
-      u64* XE = hasE ? P_<u64>(xr) : nullptr;
-      u64* XT = hasI ? P_<u64>(xr) + (hasE ? Ue : 0) * ldM : nullptr;
-      const int32_t* const none = nullptr;
-      if (hasE) {
-        auto CONN_EXPAND = ldCe <= CONN_STAGE_W ? k_conn_expand<true> : k_conn_expand<false>;
-        hipExtLaunchKernelGGL(CONN_EXPAND, dim3(nblk(ldM, K8S_XW), nblk(Ue, K8S_XR)), dim3(TPB), 0,
-                              ctx->stream, nullptr, nullptr, 0, (const u64*)P_<u64>(re), ldCe,
-                              none, cce, (const u64*)nullptr, (i64)0, none, none, 0, (i64)0, Ue,
-                              n, W, XE, ldM);
-        KLAUNCH();
-      }
-      if (hasI) {
-        auto CONN_EXPAND = KWi <= CONN_STAGE_W ? k_conn_expand<true> : k_conn_expand<false>;
-        hipExtLaunchKernelGGL(CONN_EXPAND, dim3(nblk(ldM, K8S_XW), nblk(Xi, K8S_XR)), dim3(TPB), 0,
-                              ctx->stream, nullptr, nullptr, 0, (const u64*)nullptr, (i64)0, none,
-                              none, (const u64*)P_<u64>(ti), KWi, none, rci, 0, (i64)0, Xi, n, W,
-                              XT, ldM);
-        KLAUNCH();
-      }
-      hipLaunchKernelGGL(k_conn_rows, dim3(nblk(rl * (ldM / 2))), dim3(TPB), 0, ctx->stream,
-                         (const u64*)XE, rce, (const u64*)XT, cci, self, r0, rl, ldM,
-                         P_<u64>(dst->M));
-      KLAUNCH();
-    } else {
-      // class rows of <= CONN_STAGE_W words together are staged in LDS by the expansion
-      const bool stage = (hasE ? ldCe : 0) + (hasI ? KWi : 0) <= CONN_STAGE_W;
-      auto CONN_EXPAND = stage ? k_conn_expand<true> : k_conn_expand<false>;
-      hipExtLaunchKernelGGL(CONN_EXPAND, dim3(nblk(ldM, K8S_XW), nblk(rl, K8S_XR)), dim3(TPB), 0,
-                            ctx->stream, nullptr, nullptr, 0,
-                            (const u64*)(hasE ? P_<u64>(re) : nullptr), ldCe, rce, cce,
-                            (const u64*)(hasI ? P_<u64>(ti) : nullptr), KWi, cci, rci, self, r0,
-                            rl, n, W, P_<u64>(dst->M), ldM);
-      KLAUNCH();
-    }
+    KTRY(wr.launch(eg, in, dst, flags, hasE, hasI, hasE ? P_<u64>(re) : nullptr,
+                   hasI ? P_<u64>(ri) : nullptr));
     KTRY(tev.stop(ctx, &dst->conn_ms));
     KCHK(hipMemcpyAsync(iso, cnt.p, sizeof(iso), hipMemcpyDeviceToHost, ctx->stream));
     return sync(ctx);
   };
   if (n > 0 && rl > 0) {
     const int rc = run();
-    derived_end(dst, {&ke, &ki, &re, &ri, &ti, &xr, &cnt}, rc);
+    derived_end(dst, {&ke, &ki, &re, &ri, &wr.ti, &wr.xr, &cnt}, rc);
     if (rc) return rc;
   }
   if (info) {
@@ -2304,6 +2341,134 @@ int kano_k8s_isolated(kano_ctx* ctx, uint8_t* out) {
   const int rc = run();
   free_temps(ctx, rc, {&flag, &cnt});
   return rc;
+}
+
+// The tiers (k_conn_tier_*, kano_k8s_tiers.hpp): the class-level rows come
+// from the codes' ordered copy instead of a keep mask; the write is
+// kano_k8s_conn's own.
+int kano_k8s_conn_tiers(kano_ctx* eg, kano_ctx* in, kano_ctx* dst, int flags, int64_t nids_e,
+                        const uint32_t* code_e, uint32_t np_level_e, int64_t nids_i,
+                        const uint32_t* code_i, uint32_t np_level_i, uint8_t* iso_e,
+                        uint8_t* iso_i, int64_t* info) {
+  const char* const what = "kano_k8s_conn_tiers";
+  KTRY(conn_begin(eg, in, dst, what, nids_e, nids_i));
+  kano_ctx* ctx = dst;
+  const i64 n = dst->n, rl = rows_local(dst);
+  kano_ctx* const src[2] = {eg, in};
+  const uint32_t* const code[2] = {code_e, code_i};
+  const uint32_t np[2] = {np_level_e, np_level_i};
+  const i64 nids[2] = {nids_e, nids_i};
+  uint8_t* const iso_out[2] = {iso_e, iso_i};
+  const char* const side_name[2] = {"egress", "ingress"};
+  i64 live[2] = {0, 0};
+  for (int side = 0; side < 2; ++side) {
+    const std::string w = std::string(what) + ": " + side_name[side] + " ";
+    if (nids[side] > 0 && !code[side]) return fail(dst, -EINVAL, w + "codes are NULL");
+    if (np[side] >= TIER_MAX_LEVEL)
+      return fail(dst, -EINVAL, w + "np_level is 2^30 or more");
+    for (i64 p = 0; p < nids[side]; ++p) {
+      const uint32_t c = code[side][p];
+      if (c == TIER_DROPPED) continue;
+      const uint32_t lv = c >> 2, act = c & 3u;
+      const char* bad = act == TIER_PASS && lv >= np[side]      ? "passes at or above np_level"
+                        : act == TIER_ISOLATE && lv != np[side] ? "only isolates off np_level"
+                        : act == TIER_DENY && lv == np[side]    ? "denies at np_level"
+                                                                : nullptr;
+      if (bad)
+        return fail(dst, -EINVAL, w + "code " + std::to_string(p) + " (level " +
+                                      std::to_string(lv) + ") " + bad);
+      ++live[side];
+    }
+  }
+  const bool has[2] = {conn_classes(eg), conn_classes(in)};
+  unsigned long long cnt_h[2] = {0, 0};
+  dst->conn_ms = 0.f;
+  DBuf key[2], pk[2], olist[2], okey[2], ocnt[2], hasnp[2], r[2], flag[2], cnt;
+  ConnWrite wr;
+  auto run = [&]() -> int {
+    // cnt: the isolated pods of the two sides, then k_verdict_order's scratch word
+    KTRY(dalloc(ctx, cnt, sizeof(unsigned long long) * 3));
+    for (int side = 0; side < 2; ++side) {
+      if (!has[side]) continue;
+      kano_ctx* s = src[side];
+      const size_t nnz = (size_t)std::max<i64>(1, s->nnz_sel);
+      KTRY(dalloc(ctx, key[side], sizeof(uint32_t) * (size_t)nids[side]));
+      KTRY(dalloc(ctx, pk[side], sizeof(u64) * nnz));
+      KTRY(dalloc(ctx, olist[side], sizeof(int32_t) * nnz));
+      KTRY(dalloc(ctx, okey[side], sizeof(uint32_t) * nnz));
+      KTRY(dalloc(ctx, ocnt[side], sizeof(int32_t) * (size_t)s->rc.U));
+      KTRY(dalloc(ctx, hasnp[side], (size_t)s->rc.U));
+      KTRY(dalloc(ctx, r[side], sizeof(u64) * (size_t)(s->rc.U * s->ldC)));
+      if (iso_out[side]) KTRY(dalloc(ctx, flag[side], (size_t)n));
+      KCHK(hipMemcpyAsync(key[side].p, code[side], sizeof(uint32_t) * (size_t)nids[side],
+                          hipMemcpyHostToDevice, ctx->stream));
+    }
+    // (a shard without rows still answers the isolation flags and counts)
+    if (rl > 0) KTRY(wr.alloc(eg, in, dst, flags, has[0], has[1]));
+    EventPair<> tev;
+    if (dst->stage_timing) KTRY(tev.start(ctx));
+    KCHK(hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long) * 3, ctx->stream));
+    for (int side = 0; side < 2; ++side) {
+      if (!has[side]) continue;
+      kano_ctx* s = src[side];
+      int wl;
+      i64 cap;
+      derived_shape(ctx, s->ldC, &wl, &cap);
+      hipLaunchKernelGGL(k_verdict_order, dim3((unsigned)std::min<i64>(s->rc.U, cap)), dim3(TPB), 0,
+                         ctx->stream, s->rc.U, (const i64*)P_<i64>(s->soffc),
+                         (const int32_t*)P_<int32_t>(s->slist),
+                         (const uint32_t*)P_<uint32_t>(key[side]), P_<u64>(pk[side]),
+                         P_<int32_t>(olist[side]), P_<uint32_t>(okey[side]),
+                         P_<int32_t>(ocnt[side]),
+                         reinterpret_cast<unsigned*>(P_<unsigned long long>(cnt) + 2));
+      KLAUNCH();
+      const i64 cpb = TPB / wl;
+      hipLaunchKernelGGL(k_conn_tier_class,
+                         dim3((unsigned)std::min<i64>((s->rc.U + cpb - 1) / cpb, cap)), dim3(TPB),
+                         0, ctx->stream, s->rc.U, (const i64*)P_<i64>(s->soffc),
+                         (const int32_t*)P_<int32_t>(olist[side]),
+                         (const uint32_t*)P_<uint32_t>(okey[side]),
+                         (const int32_t*)P_<int32_t>(ocnt[side]), np[side],
+                         (const u64*)P_<u64>(s->AC), s->ldC, wl, P_<u64>(r[side]),
+                         P_<uint8_t>(hasnp[side]));
+      KLAUNCH();
+      if (!info && !iso_out[side]) continue;
+      hipLaunchKernelGGL(k_conn_tier_isolated, dim3(nblk(n)), dim3(TPB), 0, ctx->stream,
+                         (const int32_t*)P_<int32_t>(s->rc.cls),
+                         (const uint8_t*)P_<uint8_t>(hasnp[side]), n,
+                         iso_out[side] ? P_<uint8_t>(flag[side]) : (uint8_t*)nullptr,
+                         P_<unsigned long long>(cnt) + side);
+      KLAUNCH();
+    }
+    if (rl > 0)
+      KTRY(wr.launch(eg, in, dst, flags, has[0], has[1], has[0] ? P_<u64>(r[0]) : nullptr,
+                     has[1] ? P_<u64>(r[1]) : nullptr));
+    KTRY(tev.stop(ctx, &dst->conn_ms));
+    for (int side = 0; side < 2; ++side)
+      if (has[side] && iso_out[side])
+        KCHK(hipMemcpyAsync(iso_out[side], flag[side].p, (size_t)n, hipMemcpyDeviceToHost,
+                            ctx->stream));
+    KCHK(hipMemcpyAsync(cnt_h, cnt.p, sizeof(cnt_h), hipMemcpyDeviceToHost, ctx->stream));
+    return sync(ctx);
+  };
+  // a side without classes isolates nobody (also where nothing is launched)
+  for (int side = 0; side < 2; ++side)
+    if (iso_out[side] && n > 0) std::memset(iso_out[side], 0, (size_t)n);
+  if (n > 0) {
+    const int rc = run();
+    derived_end(dst, {&key[0], &key[1], &pk[0], &pk[1], &olist[0], &olist[1], &okey[0], &okey[1],
+                      &ocnt[0], &ocnt[1], &hasnp[0], &hasnp[1], &r[0], &r[1], &flag[0], &flag[1],
+                      &wr.ti, &wr.xr, &cnt},
+                rc);
+    if (rc) return rc;
+  }
+  if (info) {
+    info[0] = (int64_t)cnt_h[0];
+    info[1] = (int64_t)cnt_h[1];
+    info[2] = live[0];
+    info[3] = live[1];
+  }
+  return 0;
 }
 
 int kano_k8s_conn_time(kano_ctx* ctx, float* ms) {

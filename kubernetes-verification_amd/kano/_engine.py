@@ -242,6 +242,29 @@ class DeviceBuild:
         return dict(zip(("egress_isolated", "ingress_isolated", "egress_entries",
                          "ingress_entries"), map(int, info)))
 
+    def k8s_conn_tiers_from(self, eg: "DeviceBuild", ing: "DeviceBuild", allow_self: bool,
+                            code_e, np_level_e: int, code_i, np_level_i: int,
+                            form: str = "auto"):
+        """This context's rows := the connectivity of the two builds under
+        AdminNetworkPolicy tiers (kano_k8s_conn_tiers).  ``code_e`` /
+        ``code_i``: one uint32 per engine id, level * 4 + action (0 allow,
+        1 deny, 2 pass, 3 isolates only; 0xffffffff dropped); ``np_level_*``:
+        the NetworkPolicy tier's level.  Returns (egress_isolated,
+        ingress_isolated, info): per pod "a live entry at np_level selects
+        it", and the call's counts."""
+        fbits = (1 if allow_self else 0) | {"auto": 0, "direct": 2, "stream": 4}[form]
+        ce = np.ascontiguousarray(np.asarray(code_e).reshape(-1), dtype=np.uint32)
+        ci = np.ascontiguousarray(np.asarray(code_i).reshape(-1), dtype=np.uint32)
+        iso_e = np.zeros(self.n, dtype=np.uint8)
+        iso_i = np.zeros(self.n, dtype=np.uint8)
+        info = np.zeros(4, dtype=np.int64)
+        self._chk(self.lib.kano_k8s_conn_tiers(
+            eg.ctx, ing.ctx, self.ctx, fbits, int(ce.shape[0]), _ptr(ce), int(np_level_e),
+            int(ci.shape[0]), _ptr(ci), int(np_level_i), _ptr(iso_e), _ptr(iso_i), _ptr(info)),
+            "kano_k8s_conn_tiers")
+        keys = ("egress_isolated", "ingress_isolated", "egress_entries", "ingress_entries")
+        return iso_e.astype(bool), iso_i.astype(bool), dict(zip(keys, map(int, info)))
+
     def k8s_isolated(self) -> np.ndarray:
         """Per pod: some policy of this build selects it (kano_k8s_isolated)."""
         out = np.zeros(self.n, dtype=np.uint8)

@@ -10,7 +10,8 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_double, c_float, c_int, c_int32, c_int64, c_uint8, c_uint64, c_void_p
+from ctypes import (POINTER, c_double, c_float, c_int, c_int32, c_int64, c_uint8, c_uint32,
+                    c_uint64, c_void_p)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get(
@@ -110,6 +111,9 @@ SIGNATURES = {
     "kano_k8s_edge": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "kano_k8s_conn": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int64,
                               c_void_p, c_void_p]),
+    "kano_k8s_conn_tiers": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p,
+                                    c_uint32, c_int64, c_void_p, c_uint32, c_void_p, c_void_p,
+                                    c_void_p]),
     "kano_k8s_isolated": (c_int, [c_void_p, c_void_p]),
     "kano_k8s_conn_time": (c_int, [c_void_p, POINTER(c_float)]),
     "kano_build_classes": (c_int, [c_void_p, c_int]),

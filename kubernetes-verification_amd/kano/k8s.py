@@ -76,6 +76,7 @@ it.
 """
 from __future__ import annotations
 
+import collections
 from typing import Any, Dict, List, Optional
 
 import numpy as np
@@ -123,11 +124,31 @@ class NetworkPolicy:
         return NetworkPolicy(md.get("name"), md.get("namespace"), obj.get("spec"))
 
 
+class AdminNetworkPolicy:
+    """An AdminNetworkPolicy (policy.networking.k8s.io/v1alpha1, cluster
+    scoped) over its spec dict in the manifest's camelCase: ``priority``,
+    ``subject`` and ``ingress`` / ``egress`` rules ``{action, from / to,
+    ports}``; the conformant reading's admin tier."""
+
+    def __init__(self, name: str, spec: Optional[Dict[str, Any]] = None):
+        self.name = name
+        self.spec = spec
+
+    @classmethod
+    def from_manifest(cls, obj: Dict[str, Any]):
+        return cls((obj.get("metadata") or {}).get("name"), obj.get("spec"))
+
+
+class BaselineAdminNetworkPolicy(AdminNetworkPolicy):
+    """The cluster's one BaselineAdminNetworkPolicy: ``subject`` and rules as
+    an AdminNetworkPolicy's, no priority, actions Allow and Deny."""
+
+
 def from_dict(kind: str, data: Dict[str, Any]):
     """kubesv.parser.from_dict (kubesv/kubesv/parser.py:9-18) without the
     kubernetes client: a manifest dict as this module's Pod / Namespace /
     NetworkPolicy (kind 'V1Pod', 'V1Namespace', 'V1NetworkPolicy'; the 'V1'
-    prefix is optional)."""
+    prefix is optional), or AdminNetworkPolicy / BaselineAdminNetworkPolicy."""
     k = kind[2:] if kind.startswith("V1") else kind
     md = (data or {}).get("metadata") or {}
     if k == "Pod":
@@ -136,6 +157,10 @@ def from_dict(kind: str, data: Dict[str, Any]):
         return Namespace(md.get("name"), md.get("labels"))
     if k == "NetworkPolicy":
         return NetworkPolicy.from_manifest(data)
+    if k == "AdminNetworkPolicy":
+        return AdminNetworkPolicy.from_manifest(data or {})
+    if k == "BaselineAdminNetworkPolicy":
+        return BaselineAdminNetworkPolicy.from_manifest(data or {})
     raise ValueError(f"unsupported kind {kind!r}")
 
 
@@ -401,10 +426,31 @@ def build(pods: List[Pod], policies: List[NetworkPolicy], namespaces: List[Names
 # it: matchLabels / In / Exists match nothing, NotIn / DoesNotExist always
 # hold -- so neither kano's quirk Q1 nor kubesv's quick fail (K2) applies.
 #
-# Out of scope: named ports (a string ``port`` never matches a numeric query),
-# ipBlock reachability (the matrix is pod to pod), AdminNetworkPolicy
-# (kano.algorithm.verdict_matrix is the tool for tiers), host-network pods and
-# sources with incremental updates (the two builds are made here, once).
+#
+# With AdminNetworkPolicies (``admin``) and a BaselineAdminNetworkPolicy
+# (``baseline``; policy.networking.k8s.io/v1alpha1) each direction D of a
+# subject pod x and a peer pod y (egress: x = src, y = dst; ingress: x = dst,
+# y = src) is read in three tiers:
+#   1 the D rules of all ANPs ordered by (spec.priority, position in ``admin``,
+#     rule index); a rule matches iff spec.subject selects x, one of its peers
+#     (``from`` / ``to``) selects y and it counts for the port.  The first
+#     matching rule decides: Allow, Deny, or Pass (on to 2, like no match);
+#   2 if some NetworkPolicy of type D selects x: the reading above;
+#   3 else the baseline's D rules in order, the first match decides, Allow or
+#     Deny; no match, or no baseline: allowed.
+#   allowed[s, d] = (allow_self and s == d) or (egress(s, d) and ingress(d, s))
+# ``subject`` and a peer are ``namespaces: <selector>`` (the pods of the
+# matching namespaces) or ``pods: {namespaceSelector, podSelector}`` (both
+# match); ``nodes`` / ``networks`` / ``domainNames`` peers select no pod.  Ports:
+# ``portNumber: {protocol, port}``, ``portRange: {protocol, start, end}``,
+# ``namedPort`` never matches, no ``ports`` counts for every port.  Equal
+# priorities (undefined upstream) fall back to the position in ``admin``.
+#
+# Out of scope: named ports (a string ``port`` / ``namedPort`` never matches a
+# numeric query), ipBlock reachability and the ``nodes`` / ``networks`` /
+# ``domainNames`` peers (the matrix is pod to pod), host-network pods, sources
+# with incremental updates (the two builds are made here, once) and a bulk
+# per-pair verdict call (``explain`` resolves one pair on the host).
 # ---------------------------------------------------------------------------
 
 _CONF_OPS = {"In": In, "NotIn": NotIn, "Exists": Exists, "DoesNotExist": DoesNotExist}
@@ -469,6 +515,25 @@ def rule_counts(ports, port) -> bool:
     return False
 
 
+def admin_rule_counts(ports, port) -> bool:
+    """rule_counts for an AdminNetworkPolicy / baseline rule's ``ports``:
+    ``portNumber: {protocol, port}``, ``portRange: {protocol, start, end}``;
+    ``namedPort`` never matches."""
+    if port is None or not ports:
+        return True
+    protocol, number = port
+    for e in ports:
+        e = e or {}
+        pn, pr = e.get("portNumber"), e.get("portRange")
+        if pn is not None and (pn.get("protocol") or "TCP") == protocol \
+                and pn.get("port") == number:
+            return True
+        if pr is not None and (pr.get("protocol") or "TCP") == protocol \
+                and pr.get("start") <= number <= pr.get("end"):
+            return True
+    return False
+
+
 def _port_query(port):
     if port is None:
         return None
@@ -487,11 +552,51 @@ class Conformant:
     only isolates) and the rule's ``ports``."""
 
     def __init__(self, containers, egress, ingress, origin_egress, origin_ingress,
-                 ports_egress, ports_ingress):
+                 ports_egress, ports_ingress, tiers_egress=None, tiers_ingress=None,
+                 np_level=(0, 0), tiered=False, admin_priority_ties=0):
         self.containers = containers
         self.egress, self.ingress = egress, ingress
         self.origin_egress, self.origin_ingress = origin_egress, origin_ingress
         self.ports_egress, self.ports_ingress = ports_egress, ports_ingress
+        #: per entry (kind, level, action): kind "admin" / "network" /
+        #: "baseline" says which list origin's policy index points into (0 for
+        #: the baseline); a level is one rule -- the admin rules of the
+        #: direction in evaluation order, then np_level, the one level of all
+        #: NetworkPolicy entries, then the baseline's rules; action "Allow" /
+        #: "Deny" / "Pass", or "Isolate" for the NetworkPolicy entry that only
+        #: isolates
+        network = lambda org: [("network", 0, "Allow" if o[2] is not None else "Isolate")  # noqa: E731
+                               for o in org]
+        self.tiers_egress = network(origin_egress) if tiers_egress is None else tiers_egress
+        self.tiers_ingress = network(origin_ingress) if tiers_ingress is None else tiers_ingress
+        #: the NetworkPolicy tier's level (egress, ingress) = the admin rules of the direction
+        self.np_level = tuple(np_level)
+        #: admin or baseline policies were compiled in: connectivity takes the tiered path
+        self.tiered = tiered
+        self.admin_priority_ties = admin_priority_ties
+
+    def codes(self, port):
+        """The per-entry codes (egress, ingress) of a port query, uint32:
+        level * 4 + action (0 allow, 1 deny, 2 pass, 3 isolates only) --
+        kano_k8s_conn_tiers' input.  An admin or baseline entry whose rule
+        does not count on the port is dropped (0xffffffff); a NetworkPolicy
+        entry's still isolates (action 3)."""
+        port = _port_query(port)
+        out = []
+        for tiers, ports in ((self.tiers_egress, self.ports_egress),
+                             (self.tiers_ingress, self.ports_ingress)):
+            code = np.empty(len(tiers), dtype=np.uint32)
+            for q, ((kind, level, action), rp) in enumerate(zip(tiers, ports)):
+                if kind == "network":
+                    act = 0 if action == "Allow" and rule_counts(rp, port) else 3
+                elif admin_rule_counts(rp, port):
+                    act = _ACTIONS[action]
+                else:
+                    code[q] = 0xFFFFFFFF
+                    continue
+                code[q] = level * 4 + act
+            out.append(code)
+        return tuple(out)
 
     def keep(self, port):
         """The keep masks (egress, ingress) of a port query: None for every
@@ -503,9 +608,79 @@ class Conformant:
                      for ports in (self.ports_egress, self.ports_ingress))
 
 
+_ACTIONS = {"Allow": 0, "Deny": 1, "Pass": 2}
+_NO_POD_PEERS = ("nodes", "networks", "domainNames")
+
+
+def _admin_terms(obj, what: str, ns_pod_keys: set, pod_keys: set, aliases, peer: bool):
+    """An AdminNetworkPolicy ``subject`` or peer as one kano selector dict, or
+    None when it selects no pod."""
+    obj = obj or {}
+    if peer and any(obj.get(k) is not None for k in _NO_POD_PEERS):
+        if "namespaces" in obj or "pods" in obj:
+            raise ValueError(f"{what}: more than one of namespaces / pods / "
+                             f"{' / '.join(_NO_POD_PEERS)}")
+        return None
+    if ("namespaces" in obj) == ("pods" in obj):
+        raise ValueError(f"{what}: exactly one of namespaces / pods expected")
+    if "namespaces" in obj:
+        nst, pt = _conformant_terms(obj["namespaces"], ns_pod_keys), []
+    else:
+        pd = obj["pods"] or {}
+        nst = _conformant_terms(pd.get("namespaceSelector"), ns_pod_keys)
+        pt = _conformant_terms(pd.get("podSelector"), pod_keys)
+    if nst is None or pt is None:
+        return None
+    d = _TermDict(aliases)
+    for k, r in nst:
+        d.add((_NS_LABEL, k), r)
+    for k, r in pt:
+        d.add(k, r)
+    return d.d
+
+
+def _admin_entries(pol, kind: str, actions, ns_pod_keys, pod_keys, aliases):
+    """The entries of one AdminNetworkPolicy (or the baseline) per direction:
+    {direction: [per rule: (action, ports, [(peer index, select, allow)])]},
+    one entry per pod-bearing peer; a subject selecting no pod leaves the
+    rules without entries (they keep their levels)."""
+    who = f"{kind} {pol.name!r}"
+    spec = pol.spec or {}
+    sel = _admin_terms(spec.get("subject"), f"{who}: subject", ns_pod_keys, pod_keys, aliases,
+                       peer=False)
+    out = {}
+    for direction, side in (("egress", "to"), ("ingress", "from")):
+        rules = []
+        for ri, rule in enumerate(spec.get(direction) or []):
+            rule = rule or {}
+            at = f"{who}: {direction} rule {ri}"
+            action = rule.get("action")
+            if action not in actions:
+                raise ValueError(f"{at}: action {action!r}, expected one of "
+                                 f"{' / '.join(actions)}")
+            peers = rule.get(side)
+            if not isinstance(peers, list) or not peers:
+                raise ValueError(f"{at}: a non-empty {side!r} list is required")
+            entries = []
+            for pj, peer in enumerate(peers):
+                alw = _admin_terms(peer, f"{at}: peer {pj}", ns_pod_keys, pod_keys, aliases,
+                                   peer=True)
+                if alw is not None and sel is not None:
+                    entries.append((pj, sel, alw))
+            rules.append((action, rule.get("ports"), entries))
+        out[direction] = rules
+    return out
+
+
 def compile_conformant(pods: List[Pod], policies: List[NetworkPolicy],
-                       namespaces: List[Namespace]) -> Conformant:
+                       namespaces: List[Namespace], admin=None, baseline=None) -> Conformant:
     """The conformant reading as kano objects (see the section's comment).
+    ``admin`` (AdminNetworkPolicy objects) and ``baseline`` (one
+    BaselineAdminNetworkPolicy, or a list of at most one) add their rules to
+    the same two lists, one entry per (rule, pod-bearing peer): select = the
+    subject, allow = the peer; ``tiers_*`` says per entry which tier, level
+    and action it carries.  Without them the result is the NetworkPolicy
+    reading alone.
     Every policy of a type that selects a pod-bearing selector contributes at
     least one entry per type, so "selected by some entry" is "isolated": a
     policy of a type whose rules allow nothing gets one entry whose allow side
@@ -527,6 +702,37 @@ def compile_conformant(pods: List[Pod], policies: List[NetworkPolicy],
     lists = {"egress": [], "ingress": []}
     origin = {"egress": [], "ingress": []}
     ports = {"egress": [], "ingress": []}
+    tiers = {"egress": [], "ingress": []}
+
+    def tier_entries(kind, pi, compiled, first_level):
+        """One policy's rules appended from first_level[direction] on."""
+        for direction, rules in compiled.items():
+            for ri, (action, rp, entries) in enumerate(rules):
+                for pj, sel, alw in entries:
+                    lists[direction].append((sel, alw))
+                    origin[direction].append((pi, direction, ri, pj))
+                    ports[direction].append(rp)
+                    tiers[direction].append((kind, first_level[direction] + ri, action))
+            first_level[direction] += len(rules)
+
+    admin = list(admin or [])
+    if isinstance(baseline, (list, tuple)):
+        if len(baseline) > 1:
+            raise ValueError(f"{len(baseline)} BaselineAdminNetworkPolicies: a cluster has one")
+        baseline = baseline[0] if baseline else None
+    for pol in admin:
+        prio = (pol.spec or {}).get("priority")
+        if isinstance(prio, bool) or not isinstance(prio, int) or not 0 <= prio <= 1000:
+            raise ValueError(f"admin {pol.name!r}: priority {prio!r}, expected an integer "
+                             "in 0..1000")
+    # the admin tier: the rules of a direction in (priority, position, rule) order
+    level = {"egress": 0, "ingress": 0}
+    for pi in sorted(range(len(admin)), key=lambda q: (admin[q].spec["priority"], q)):
+        tier_entries("admin", pi, _admin_entries(admin[pi], "admin", tuple(_ACTIONS), ns_pod_keys,
+                                                 pod_keys, aliases), level)
+    np_level = (level["egress"], level["ingress"])
+    prios = [a.spec["priority"] for a in admin]
+    ties = len(prios) - len(set(prios))
     for pi, pol in enumerate(policies):
         spec = pol.spec or {}
         types = policy_types(spec)
@@ -570,6 +776,13 @@ def compile_conformant(pods: List[Pod], policies: List[NetworkPolicy],
                 lists[direction].append((sel.d, alw))
                 origin[direction].append((pi, direction, ri, pj))
                 ports[direction].append(rp)
+                tiers[direction].append(("network", level[direction],
+                                         "Allow" if ri is not None else "Isolate"))
+    # the baseline tier: its rules in order, after the NetworkPolicy level
+    if baseline is not None:
+        tier_entries("baseline", 0, _admin_entries(baseline, "baseline", ("Allow", "Deny"),
+                                                   ns_pod_keys, pod_keys, aliases),
+                     {d: v + 1 for d, v in level.items()})
 
     containers = []
     for p in pods:
@@ -586,7 +799,9 @@ def compile_conformant(pods: List[Pod], policies: List[NetworkPolicy],
         return [Policy(f"k8s{q}", PolicySelect(s), PolicyAllow(a), PolicyEgress, None)
                 for q, (s, a) in enumerate(pairs)]
     return Conformant(containers, kano(lists["egress"]), kano(lists["ingress"]),
-                      origin["egress"], origin["ingress"], ports["egress"], ports["ingress"])
+                      origin["egress"], origin["ingress"], ports["egress"], ports["ingress"],
+                      tiers["egress"], tiers["ingress"], np_level,
+                      tiered=bool(admin) or baseline is not None, admin_priority_ties=ties)
 
 
 class K8sConnectivity:
@@ -612,7 +827,10 @@ class K8sConnectivity:
     def on_port(self, port) -> "K8sConnectivity":
         """The same cluster on another port: a new keep mask over the two
         resident builds and one kano_k8s_conn -- nothing is interned or
-        uploaded again."""
+        uploaded again.  With tiers: new codes and one kano_k8s_conn_tiers."""
+        if self._compiled.tiered:
+            return _connect_tiers(self.egress, self.ingress, self._compiled, self._policies,
+                                  port, self.allow_self, self._device, self._rows, self._form)
         return _connect(self.egress, self.ingress, self._compiled, self._policies, port,
                         self.allow_self, (self.egress_isolated, self.ingress_isolated),
                         self._device, self._rows, self._form)
@@ -628,6 +846,8 @@ class K8sConnectivity:
         n = self.allowed.container_size
         if not (0 <= src < n and 0 <= dst < n):
             raise IndexError("bitarray index out of range")
+        if self._compiled.tiered:
+            return self._explain_tiers(src, dst)
         keep = self._compiled.keep(self.port)
         out = {"self": bool(self.allow_self and src == dst), "blocked_by": []}
         for direction, m, pair, iso, org, kp in (
@@ -644,6 +864,63 @@ class K8sConnectivity:
             isolated = bool(iso[pair[0]])
             out[direction] = {"isolated": isolated, "policies": pols}
             if isolated and not pols:
+                out["blocked_by"].append(direction)
+        out["allowed"] = out["self"] or not out["blocked_by"]
+        return out
+
+    def _explain_tiers(self, src: int, dst: int) -> dict:
+        """explain with AdminNetworkPolicy tiers: per direction additionally
+        ``tier`` ("admin" / "network" / "baseline" / "default"), ``verdict``
+        ("allow" / "deny"), ``decider`` ((kind, policy name, rule index, peer
+        index, action) or None) and -- where a Pass rule handed the pair down
+        -- ``passed``, that rule named like a decider.  Resolved here from the
+        entries matching the pair (kano_pair_policies) and the port's codes."""
+        c = self._compiled
+        codes = c.codes(self.port)
+        out = {"self": bool(self.allow_self and src == dst), "blocked_by": []}
+        for k, (direction, m, pair, iso, org, tiers) in enumerate((
+                ("egress", self.egress, (src, dst), self.egress_isolated,
+                 c.origin_egress, c.tiers_egress),
+                ("ingress", self.ingress, (dst, src), self.ingress_isolated,
+                 c.origin_ingress, c.tiers_ingress))):
+            ids = []
+            if org:
+                r = m.engine.pair_policies([pair], lists=True)
+                ids = r["policies"][r["offsets"][0]:r["offsets"][1]].tolist()
+            code, np_level = codes[k], c.np_level[k]
+            # the live matching entries in evaluation order: (code, id)
+            live = sorted((int(code[p]), p) for p in ids if code[p] != 0xFFFFFFFF)
+
+            def name(p):
+                kind = tiers[p][0]
+                return (kind, self._policies[kind][org[p][0]].name, org[p][2], org[p][3],
+                        tiers[p][2])
+
+            isolated = bool(iso[pair[0]])
+            d = {"isolated": isolated,
+                 "policies": [name(p)[1:4] for cd, p in live if cd == np_level * 4]}
+            tier = verdict = decider = None
+            if live and live[0][0] >> 2 < np_level:       # the first matching admin rule
+                cd, p = live[0]
+                if cd & 3 == 2:
+                    d["passed"] = name(p)
+                else:
+                    tier, decider = "admin", name(p)
+                    verdict = "allow" if cd & 3 == 0 else "deny"
+            if tier is None and isolated:
+                allow = [p for cd, p in live if cd == np_level * 4]
+                tier, verdict = "network", "allow" if allow else "deny"
+                decider = name(allow[0]) if allow else None
+            if tier is None:
+                tier, verdict = "default", "allow"
+                for cd, p in live:
+                    if cd >> 2 > np_level:
+                        tier, decider = "baseline", name(p)
+                        verdict = "allow" if cd & 3 == 0 else "deny"
+                        break
+            d.update(tier=tier, verdict=verdict, decider=decider)
+            out[direction] = d
+            if verdict == "deny":
                 out["blocked_by"].append(direction)
         out["allowed"] = out["self"] or not out["blocked_by"]
         return out
@@ -671,13 +948,48 @@ def _connect(egress, ingress, compiled, policies, port, allow_self, isolated, de
                            bool(allow_self), info, isolated, device, rows, form)
 
 
+def _connect_tiers(egress, ingress, compiled, policies, port, allow_self, device, rows,
+                   form="auto"):
+    """_connect with AdminNetworkPolicy tiers: the port's codes over the two
+    resident builds and one kano_k8s_conn_tiers, which also answers the
+    isolation flags."""
+    from ._engine import DeviceBuild
+    n = len(compiled.containers)
+    port = _port_query(port)
+    code_e, code_i = compiled.codes(port)
+    out = DeviceBuild.empty(n, device=device, rows=rows)
+    iso_e, iso_i, counts = out.k8s_conn_tiers_from(
+        egress.engine, ingress.engine, allow_self, code_e, compiled.np_level[0], code_i,
+        compiled.np_level[1], form)
+    kinds = [t[0] for t in compiled.tiers_egress + compiled.tiers_ingress]
+    info = {"egress_entries": len(compiled.egress), "ingress_entries": len(compiled.ingress),
+            "kept_egress_entries": counts["egress_entries"],
+            "kept_ingress_entries": counts["ingress_entries"],
+            "egress_isolated": counts["egress_isolated"],
+            "ingress_isolated": counts["ingress_isolated"],
+            "port": port, "allow_self": bool(allow_self), "rows": rows,
+            "admin_entries": kinds.count("admin"), "baseline_entries": kinds.count("baseline"),
+            "admin_levels": sum(compiled.np_level),
+            "admin_priority_ties": compiled.admin_priority_ties}
+    return K8sConnectivity(_wrap(out, n), egress, ingress, compiled, policies, port,
+                           bool(allow_self), info, (iso_e, iso_i), device, rows, form)
+
+
 def connectivity(pods: List[Pod], policies: List[NetworkPolicy], namespaces: List[Namespace],
                  port=None, allow_self: bool = True, device: int = 0, path: str = "auto",
-                 rows: Optional[tuple] = None, form: str = "auto") -> K8sConnectivity:
+                 rows: Optional[tuple] = None, form: str = "auto", admin=None,
+                 baseline=None) -> K8sConnectivity:
     """The connectivity a cluster enforces (networking.k8s.io/v1) as an n x n
     matrix on the device (rows src, columns dst).  ``port``: None -- every
     rule counts whatever its ports, an upper bound over ports -- or
-    (protocol, number).  ``allow_self``: a pod always reaches itself.
+    (protocol, number).  ``admin`` / ``baseline``: the cluster's
+    AdminNetworkPolicies and its BaselineAdminNetworkPolicy (see the section's
+    comment), resolved per tier on the device; with Deny or Pass rules that
+    carry ``ports``, ``port=None`` still counts every rule and is then no
+    longer an upper bound over ports.  ``info`` gains ``admin_entries``,
+    ``baseline_entries``, ``admin_levels`` (rules, both directions) and
+    ``admin_priority_ties`` (ANPs sharing their priority with an earlier one:
+    the position in ``admin`` breaks the tie).  ``allow_self``: a pod always reaches itself.
     ``rows=(r0, r1)``: only those rows (a multi-GPU rank's shard).  ``form``:
     how the rows are written -- "direct" (gathered from the two class-level
     tables), "stream" (the tables' class rows expanded once, then streamed) or
@@ -688,7 +1000,7 @@ def connectivity(pods: List[Pod], policies: List[NetworkPolicy], namespaces: Lis
     if form not in ("auto", "direct", "stream"):
         raise ValueError(f"form must be 'auto', 'direct' or 'stream', not {form!r}")
     policies = list(policies)
-    compiled = compile_conformant(pods, policies, namespaces)
+    compiled = compile_conformant(pods, policies, namespaces, admin, baseline)
 
     def operand(pols):
         b = DeviceBuild(intern(compiled.containers, pols), device=device, path=path, build=False)
@@ -696,8 +1008,14 @@ def connectivity(pods: List[Pod], policies: List[NetworkPolicy], namespaces: Lis
         return b
 
     eg, ing = operand(compiled.egress), operand(compiled.ingress)
-    isolated = (eg.k8s_isolated(), ing.k8s_isolated())
     n = len(pods)
+    if compiled.tiered:
+        if isinstance(baseline, (list, tuple)):
+            baseline = baseline[0] if baseline else None
+        by_kind = {"admin": list(admin or []), "network": policies, "baseline": [baseline]}
+        return _connect_tiers(_wrap(eg, n), _wrap(ing, n), compiled, by_kind, port, allow_self,
+                              device, rows, form)
+    isolated = (eg.k8s_isolated(), ing.k8s_isolated())
     return _connect(_wrap(eg, n), _wrap(ing, n), compiled, policies, port, allow_self, isolated,
                     device, rows, form)
 
@@ -712,6 +1030,27 @@ def load_manifests(paths):
     ignored.  A namespace that is referenced but not declared is created, and
     every namespace gets the ``kubernetes.io/metadata.name`` label if it lacks
     it."""
+    return _load(paths)[:3]
+
+
+Cluster = collections.namedtuple("Cluster", "pods policies namespaces admin baseline")
+
+
+def load_cluster(paths) -> Cluster:
+    """load_manifests plus the kinds AdminNetworkPolicy (``admin``, in file
+    order) and BaselineAdminNetworkPolicy (``baseline``: the one object, or
+    None; a second one is a ValueError): a named tuple (pods, policies,
+    namespaces, admin, baseline), ready for ``connectivity(*c[:3],
+    admin=c.admin, baseline=c.baseline)``."""
+    pods, pols, nss, admin, base = _load(paths)
+    if len(base) > 1:
+        raise ValueError(f"{len(base)} BaselineAdminNetworkPolicies: a cluster has one")
+    return Cluster(pods, pols, nss, admin, base[0] if base else None)
+
+
+def _load(paths):
+    """(pods, policies, namespaces, AdminNetworkPolicies,
+    BaselineAdminNetworkPolicies) of the manifests."""
     import os
     import yaml
     if isinstance(paths, (str, os.PathLike)):
@@ -726,7 +1065,7 @@ def load_manifests(paths):
                           if f.endswith((".yaml", ".yml", ".json"))]
         else:
             files.append(p)
-    pods, pols, nss = [], [], {}
+    pods, pols, nss, admin, base = [], [], {}, [], []
 
     def take(obj):
         if not isinstance(obj, dict):
@@ -742,6 +1081,10 @@ def load_manifests(paths):
         elif kind == "Namespace":
             ns = from_dict("Namespace", obj)
             nss[ns.name] = ns
+        elif kind == "AdminNetworkPolicy":
+            admin.append(from_dict(kind, obj))
+        elif kind == "BaselineAdminNetworkPolicy":
+            base.append(from_dict(kind, obj))
 
     for f in files:
         with open(f) as fh:
@@ -752,4 +1095,4 @@ def load_manifests(paths):
             nss[o.namespace] = Namespace(o.namespace)
     for ns in nss.values():
         ns.labels.setdefault(_NS_NAME_LABEL, ns.name)
-    return pods, pols, list(nss.values())
+    return pods, pols, list(nss.values()), admin, base

@@ -6,7 +6,10 @@ egress to a few apps -- timed per stage.  One JSON line per size.
 
 Usage: python scripts/k8s_bench.py [--pods 10000 100000] [--reps 3]
        python scripts/k8s_bench.py --conn ...   (the conformant reading,
-       kano.k8s.connectivity, over the same cluster)"""
+       kano.k8s.connectivity, over the same cluster)
+       python scripts/k8s_bench.py --conn --admin 50 --baseline ...   (the same
+       with 50 generated AdminNetworkPolicies and a default-deny baseline: the
+       tiered call's times next to the plain call's of the same run)"""
 import argparse
 import json
 import os
@@ -50,6 +53,90 @@ def cluster(n, seed=0):
                 "podSelector": {"matchLabels": {"app": f"a{a}"}},
                 "ingress": [{"from": ing}], "egress": [{"to": egr}]}))
     return pods, pols, nss
+
+
+def admin_policies(K, baseline, nns, seed=1):
+    """K AdminNetworkPolicies over cluster()'s labels -- mixed actions,
+    namespace and pod subjects, some rules with ports -- and, on request, a
+    default-deny BaselineAdminNetworkPolicy."""
+    from kano import k8s
+    rng = np.random.default_rng(seed)
+    teams = ["a", "b", "c", "d"]
+
+    def who():
+        r = rng.random()
+        if r < 0.4:
+            return {"namespaces": {"matchLabels": {"team": teams[int(rng.integers(4))]}}}
+        pods = {"podSelector": {"matchLabels": {"app": f"a{int(rng.integers(20))}"}}}
+        if r < 0.7:
+            pods["namespaceSelector"] = {"matchLabels": {"team": teams[int(rng.integers(4))]}}
+        return {"pods": pods}
+
+    def rules(side):
+        out = []
+        for _ in range(int(rng.integers(1, 4))):
+            rule = {"action": ["Allow", "Deny", "Pass"][int(rng.integers(3))],
+                    side: [who() for _ in range(int(rng.integers(1, 3)))]}
+            if rng.random() < 0.3:
+                rule["ports"] = [{"portNumber": {"protocol": "TCP", "port": 80}},
+                                 {"portRange": {"protocol": "TCP", "start": 8000, "end": 8100}}][
+                                     :int(rng.integers(1, 3))]
+            out.append(rule)
+        return out
+
+    admin = [k8s.AdminNetworkPolicy(f"anp{q}", {
+        "priority": int(rng.integers(0, 1001)), "subject": who(),
+        "egress": rules("to"), "ingress": rules("from")}) for q in range(K)]
+    base = None
+    if baseline:
+        base = k8s.BaselineAdminNetworkPolicy("default", {
+            "subject": {"namespaces": {}},
+            "egress": [{"action": "Allow", "to": [{"namespaces": {"matchLabels": {"team": "a"}}}]},
+                       {"action": "Deny", "to": [{"namespaces": {}}]}],
+            "ingress": [{"action": "Deny", "from": [{"namespaces": {}}]}]})
+    return admin, base
+
+
+def conn_tiers(args, n, pods, pols, nss, rows):
+    """The tiered call (kano_k8s_conn_tiers) over the builds of the same
+    cluster with the generated admin and baseline policies compiled in."""
+    from kano import k8s
+    from kano._engine import DeviceBuild
+    from kano._intern import intern
+    admin, base = admin_policies(args.admin, args.baseline, len(nss))
+    t = time.perf_counter()
+    c = k8s.compile_conformant(pods, pols, nss, admin, base)
+    t_compile = time.perf_counter() - t
+    te, ti = intern(c.containers, c.egress), intern(c.containers, c.ingress)
+    code, code_port = c.codes(None), c.codes(("TCP", 8050))   # (drops the port-80-only rules)
+    best = None
+    for _ in range(args.reps):
+        eg, ing = DeviceBuild(te, build=False), DeviceBuild(ti, build=False)
+        eg.build_classes()
+        ing.build_classes()
+        out = DeviceBuild.empty(n, rows=rows)
+        out.k8s_conn_tiers_from(eg, ing, True, code_port[0], c.np_level[0], code_port[1],
+                                c.np_level[1], args.conn_form)          # a port query first
+        dev_port = out.k8s_conn_time()
+        t2 = time.perf_counter()
+        _, _, info = out.k8s_conn_tiers_from(eg, ing, True, code[0], c.np_level[0], code[1],
+                                             c.np_level[1], args.conn_form)
+        t3 = time.perf_counter()
+        r = (t3 - t2, out.k8s_conn_time(), dev_port)
+        best = r if best is None or r[1] < best[1] else best
+        ie, ii = eg.info(), ing.info()
+        del eg, ing
+    kinds = [t[0] for t in c.tiers_egress + c.tiers_ingress]
+    return {"admin_policies": len(admin), "baseline": base is not None,
+            "admin_entries": kinds.count("admin"), "baseline_entries": kinds.count("baseline"),
+            "admin_levels": list(c.np_level), "admin_priority_ties": c.admin_priority_ties,
+            "egress_entries": len(c.egress), "ingress_entries": len(c.ingress),
+            "egress_classes": [ie["U"], ie["UA"]], "ingress_classes": [ii["U"], ii["UA"]],
+            "host_compile_s": round(t_compile, 3),
+            "conn_tiers_ms": round(best[0] * 1e3, 3), "conn_tiers_device_ms": round(best[1], 4),
+            "conn_tiers_port_device_ms": round(best[2], 4),
+            "egress_isolated": info["egress_isolated"],
+            "ingress_isolated": info["ingress_isolated"]}
 
 
 HBM_SPEC = 8.0e12   # MI355X HBM3E, bytes per second
@@ -99,6 +186,9 @@ def conn(args):
         nbytes = n * n / 8 / args.ranks
         from kano import algorithm as alg
         em = k8s._wrap(out, n)
+        tiers = {}
+        if args.admin > 0 or args.baseline:
+            tiers = {"tiers": conn_tiers(args, n, pods, pols, nss, rows)}
         print(json.dumps({
             "workload": "k8s.connectivity (conformant reading), synthetic K8s cluster",
             "form": args.conn_form,
@@ -114,7 +204,7 @@ def conn(args):
             "egress_isolated": info["egress_isolated"],
             "ingress_isolated": info["ingress_isolated"],
             "matrix_bytes": 8 * n * W, "ranks": args.ranks, "rows": n // args.ranks,
-            "all_isolated": len(alg.all_isolated(em)) if args.ranks == 1 else None}),
+            "all_isolated": len(alg.all_isolated(em)) if args.ranks == 1 else None, **tiers}),
             flush=True)
 
 
@@ -124,6 +214,11 @@ def main():
                     help="the conformant reading (kano.k8s.connectivity) instead of kubesv's edge")
     ap.add_argument("--conn-form", default="auto", choices=["auto", "direct", "stream"],
                     help="--conn: how kano_k8s_conn writes the rows")
+    ap.add_argument("--admin", type=int, default=0,
+                    help="--conn: also time kano_k8s_conn_tiers with this many generated "
+                         "AdminNetworkPolicies")
+    ap.add_argument("--baseline", action="store_true",
+                    help="--conn: ... and a default-deny BaselineAdminNetworkPolicy")
     ap.add_argument("--pods", type=int, nargs="+", default=[10000, 100000])
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--form", default="classes", choices=["classes", "pods"])
