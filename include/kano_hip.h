@@ -934,6 +934,50 @@ int kano_k8s_conn_tiers(kano_ctx* eg, kano_ctx* in, kano_ctx* dst, int flags,
 /* KANO_TUNE timing=1: the last kano_k8s_conn's or kano_k8s_conn_tiers' device
  * time in ms on its destination (the fills and the kernels, no copies), else 0. */
 int kano_k8s_conn_time(kano_ctx* ctx, float* ms);
+/* K8sConnectivity.pair_verdicts: for each of Q pod pairs (src, dst), which tier
+ * and which entry decide it under the rule of kano_k8s_conn_tiers above, per
+ * direction (egress: subject src, peer dst, build eg; ingress: subject dst,
+ * peer src, build in), from the same two builds and codes (a cluster without
+ * admin or baseline rules: np_level 0 and the codes 0 / 3).  Over the live
+ * entries selecting the subject and allowing the peer, ordered by (code, id):
+ * the first below np_level decides (tier admin) unless it passes -- then it
+ * is the passed entry; else a subject selected by a live entry at np_level
+ * (isolated; no allowing peer needed) is decided in tier network: allow by the
+ * first entry of code np_level * 4, else deny without a decider; else the first
+ * entry above np_level decides (tier baseline); else tier default, allow.  A
+ * decider is therefore the smallest engine id at the winning code.
+ *   verdict[q]: bit 0 allowed, bit 1 self traffic (src == dst and flags &
+ *   KANO_K8S_CONN_SELF), bits 2-3 the egress tier (0 default, 1 admin, 2 network,
+ *   3 baseline), bit 4 egress denies, bits 5-6 the ingress tier, bit 7 ingress
+ *   denies; allowed = self | !(bit 4 | bit 7).
+ * decider_* / passed_* (nullable, Q each): engine ids of the respective build,
+ * -1 where there is none.  counts (nullable, 18) = [allowed, self, then per
+ * egress tier 0..3 its (allow, deny) pairs, then the same 8 for ingress].
+ * Pairs in any order, duplicates allowed; only flags & KANO_K8S_CONN_SELF is
+ * read.  A side without policies has no classes: (default, allow).
+ * -EINVAL: a NULL context, pairs or verdict (Q > 0) or codes (nids > 0), Q < 0,
+ * contexts of two devices or different n, nids other than the sources' P, an
+ * np_level of 2^30 or more, a live code illegal for its level (as above);
+ * -ERANGE: a pair index outside [0, n); -ENOTSUP: a source holding a row
+ * shard, policy lists, added or removed policies or edited rows; -ENOMEM (with
+ * a message): a device buffer could not be allocated.  Errors are reported on
+ * eg; both contexts stay usable after every error.  Q == 0 or n == 0 launch
+ * nothing.  The device buffers (pairs, codes, results) are the call's own,
+ * freed on return; the sources' tables and stored results are unchanged.
+ * Two forms give the same answers: a lane per pair, or a wave per pair (taken
+ * when the two builds' mean lists together exceed 16 entries); KANO_TUNE
+ * kpf=1 / 2 forces lane / wave, kpgrid=K caps the grid at K blocks. */
+int kano_k8s_pair_verdicts(kano_ctx* eg, kano_ctx* in, int flags /* KANO_K8S_CONN_SELF */,
+                           int64_t Q, const int32_t* pairs /* 2*Q: src, dst */,
+                           int64_t nids_e, const uint32_t* code_e, uint32_t np_level_e,
+                           int64_t nids_i, const uint32_t* code_i, uint32_t np_level_i,
+                           uint8_t* verdict /* Q */,
+                           int32_t* decider_e, int32_t* passed_e, /* Q each, nullable */
+                           int32_t* decider_i, int32_t* passed_i,
+                           int64_t* counts /* 18, nullable */);
+/* KANO_TUNE timing=1: the last kano_k8s_pair_verdicts' device time in ms on
+ * eg (the kernel, no copies), else 0. */
+int kano_k8s_pair_verdicts_time(kano_ctx* eg, float* ms);
 
 /* kano_build without the matrix write (model.py:125-165 up to the class-level
  * matrix Mc, the lists and the column checks): M is written on first use

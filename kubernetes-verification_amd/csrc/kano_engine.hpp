@@ -176,6 +176,8 @@ struct kano_ctx {
   int pmask_grid = 0;        // pmgrid=K: at most K blocks for k_pmask_lane / k_pmask_wave (0: 8 per CU)
   int verdict_form = 0;      // pvf=1/2: kano_pair_verdicts' lane / wave form forced (0: as pair_policies')
   int verdict_grid = 0;      // pvgrid=K: at most K blocks for k_verdict_lane / k_verdict_wave (0: 8 per CU)
+  int kpair_form = 0;        // kpf=1/2: kano_k8s_pair_verdicts' lane / wave form forced (0: by the two lists' length)
+  int kpair_grid = 0;        // kpgrid=K: at most K blocks for k_k8s_pair_lane / k_k8s_pair_wave (0: 8 per CU)
   int diff_grid = 0;         // dgrid=K: at most K blocks for k_diff_rows (0: every resident block)
   int group_grid = 0;        // ggrid=K: at most K blocks for k_group_rows (0: every resident block)
   int group_batches = 0;     // gbatch=K: at most K batches of 64 destination groups in one
@@ -320,6 +322,9 @@ struct kano_ctx {
   // k8s.connectivity (kano_k8s_conn, in the destination context): the device
   // buffers are the call's own; only the time stays
   float conn_ms = 0.f;        // timing=1: the last kano_k8s_conn's fills + kernels
+  // K8sConnectivity.pair_verdicts (kano_k8s_pair_verdicts, in the egress
+  // context): the device buffers are the call's own; only the time stays
+  float kpair_ms = 0.f;       // timing=1: the last kano_k8s_pair_verdicts' kernel
   // reverse_matrix / reach_zones (kano_reverse, in the destination context;
   // kano_zones, in the first): the device buffers are the call's own; only
   // the times stay
@@ -515,6 +520,11 @@ int pairs_check(kano_ctx* ctx, const char* what, i64 Q, const int32_t* pairs, i6
 int pair_tables(kano_ctx* ctx, const char* what, const int32_t* pairs_dev, i64 Q, PairTables& t);
 void pair_shape(const kano_ctx* ctx, const PairTables& t, int form_knob, int grid_knob, i64 Q,
                 bool* wave, unsigned* grid);
+// ... and for a call whose pairs walk the lists of several builds
+// (kano_k8s_pair_verdicts): pair_mean_walk of each, the shape from their sum
+i64 pair_mean_walk(const kano_ctx* ctx, const PairTables& t);
+void pair_shape(const kano_ctx* ctx, i64 mean_walk, int form_knob, int grid_knob, i64 Q, bool* wave,
+                unsigned* grid);
 
 // matrix_diff's launches (kano_hip.hip, next to the kernels; the entry points
 // are kano_ext.hip's)

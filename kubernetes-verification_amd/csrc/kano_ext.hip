@@ -8,6 +8,7 @@
 #include "kano_inc.hpp"
 #include "kano_k8s.hpp"
 #include "kano_k8s_conn.hpp"
+#include "kano_k8s_pairs.hpp"
 #include "kano_k8s_tiers.hpp"
 #include "kano_path.hpp"
 #include "kano_hops.hpp"
@@ -2206,6 +2207,26 @@ struct ConnWrite {
   }
 };
 
+// one value per engine id of each source
+int conn_nids(const kano_ctx* eg, const kano_ctx* in, kano_ctx* err_ctx, const char* what,
+              i64 nids_e, i64 nids_i) {
+  if (nids_e != eg->P || nids_i != in->P)
+    return fail(err_ctx, -EINVAL, std::string(what) + ": nids = " + std::to_string(nids_e) +
+                                      " / " + std::to_string(nids_i) + ", the sources have " +
+                                      std::to_string(eg->P) + " / " + std::to_string(in->P) +
+                                      " engine ids");
+  return 0;
+}
+
+// the sources' classes are complete
+int conn_sync(kano_ctx* eg, kano_ctx* in, kano_ctx* err_ctx, const char* what) {
+  for (kano_ctx* s : {eg, in}) {
+    const int rc = sync(s);
+    if (rc) return s == err_ctx ? rc : fail(err_ctx, rc, std::string(what) + ": source: " + s->err);
+  }
+  return 0;
+}
+
 // The shared preamble of kano_k8s_conn and kano_k8s_conn_tiers: the three
 // contexts checked and ready, the sources' classes complete.  Errors on dst.
 int conn_begin(kano_ctx* eg, kano_ctx* in, kano_ctx* dst, const char* what, i64 nids_e,
@@ -2224,16 +2245,36 @@ int conn_begin(kano_ctx* eg, kano_ctx* in, kano_ctx* dst, const char* what, i64 
   const i64 n = dst->n, rl = rows_local(dst);
   if (eg->n != n || in->n != n)
     return fail(dst, -EINVAL, w + ": the three contexts must hold the same pods");
-  if (nids_e != eg->P || nids_i != in->P)
-    return fail(dst, -EINVAL, w + ": nids = " + std::to_string(nids_e) + " / " +
-                                  std::to_string(nids_i) + ", the sources have " +
-                                  std::to_string(eg->P) + " / " + std::to_string(in->P) +
-                                  " engine ids");
+  KTRY(conn_nids(eg, in, dst, what, nids_e, nids_i));
   if ((rl + K8S_XR - 1) / K8S_XR > 65535)   // (k_conn_expand's grid)
     return fail(dst, -ENOTSUP, w + ": more than 4,194,240 rows in one context");
-  for (kano_ctx* s : {eg, in}) {
-    const int rc = sync(s);   // the sources' classes are complete
-    if (rc) return fail(dst, rc, w + ": source: " + s->err);
+  return conn_sync(eg, in, dst, what);
+}
+
+// The codes of kano_k8s_conn_tiers and kano_k8s_pair_verdicts checked ([0]
+// egress, [1] ingress); live[side] = the codes that are not dropped.
+int tier_codes_check(kano_ctx* err_ctx, const char* what, const i64 nids[2],
+                     const uint32_t* const code[2], const uint32_t np[2], i64 live[2]) {
+  const char* const side_name[2] = {"egress", "ingress"};
+  live[0] = live[1] = 0;
+  for (int side = 0; side < 2; ++side) {
+    const std::string w = std::string(what) + ": " + side_name[side] + " ";
+    if (nids[side] > 0 && !code[side]) return fail(err_ctx, -EINVAL, w + "codes are NULL");
+    if (np[side] >= TIER_MAX_LEVEL)
+      return fail(err_ctx, -EINVAL, w + "np_level is 2^30 or more");
+    for (i64 p = 0; p < nids[side]; ++p) {
+      const uint32_t c = code[side][p];
+      if (c == TIER_DROPPED) continue;
+      const uint32_t lv = c >> 2, act = c & 3u;
+      const char* bad = act == TIER_PASS && lv >= np[side]      ? "passes at or above np_level"
+                        : act == TIER_ISOLATE && lv != np[side] ? "only isolates off np_level"
+                        : act == TIER_DENY && lv == np[side]    ? "denies at np_level"
+                                                                : nullptr;
+      if (bad)
+        return fail(err_ctx, -EINVAL, w + "code " + std::to_string(p) + " (level " +
+                                          std::to_string(lv) + ") " + bad);
+      ++live[side];
+    }
   }
   return 0;
 }
@@ -2359,27 +2400,8 @@ int kano_k8s_conn_tiers(kano_ctx* eg, kano_ctx* in, kano_ctx* dst, int flags, in
   const uint32_t np[2] = {np_level_e, np_level_i};
   const i64 nids[2] = {nids_e, nids_i};
   uint8_t* const iso_out[2] = {iso_e, iso_i};
-  const char* const side_name[2] = {"egress", "ingress"};
-  i64 live[2] = {0, 0};
-  for (int side = 0; side < 2; ++side) {
-    const std::string w = std::string(what) + ": " + side_name[side] + " ";
-    if (nids[side] > 0 && !code[side]) return fail(dst, -EINVAL, w + "codes are NULL");
-    if (np[side] >= TIER_MAX_LEVEL)
-      return fail(dst, -EINVAL, w + "np_level is 2^30 or more");
-    for (i64 p = 0; p < nids[side]; ++p) {
-      const uint32_t c = code[side][p];
-      if (c == TIER_DROPPED) continue;
-      const uint32_t lv = c >> 2, act = c & 3u;
-      const char* bad = act == TIER_PASS && lv >= np[side]      ? "passes at or above np_level"
-                        : act == TIER_ISOLATE && lv != np[side] ? "only isolates off np_level"
-                        : act == TIER_DENY && lv == np[side]    ? "denies at np_level"
-                                                                : nullptr;
-      if (bad)
-        return fail(dst, -EINVAL, w + "code " + std::to_string(p) + " (level " +
-                                      std::to_string(lv) + ") " + bad);
-      ++live[side];
-    }
-  }
+  i64 live[2];
+  KTRY(tier_codes_check(dst, what, nids, code, np, live));
   const bool has[2] = {conn_classes(eg), conn_classes(in)};
   unsigned long long cnt_h[2] = {0, 0};
   dst->conn_ms = 0.f;
@@ -2474,6 +2496,113 @@ int kano_k8s_conn_tiers(kano_ctx* eg, kano_ctx* in, kano_ctx* dst, int flags, in
 int kano_k8s_conn_time(kano_ctx* ctx, float* ms) {
   if (!ctx || !ms) return -EINVAL;
   *ms = ctx->conn_ms;
+  return 0;
+}
+
+// K8sConnectivity.pair_verdicts: which tier and rule decide each pair, both
+// directions in one launch (k_k8s_pair_lane / k_k8s_pair_wave,
+// kano_k8s_pairs.hpp).  Sources and codes are checked as kano_k8s_conn_tiers
+// checks them; the work runs on eg's stream and errors are reported on eg.
+int kano_k8s_pair_verdicts(kano_ctx* eg, kano_ctx* in, int flags, int64_t Q, const int32_t* pairs,
+                           int64_t nids_e, const uint32_t* code_e, uint32_t np_level_e,
+                           int64_t nids_i, const uint32_t* code_i, uint32_t np_level_i,
+                           uint8_t* verdict, int32_t* decider_e, int32_t* passed_e,
+                           int32_t* decider_i, int32_t* passed_i, int64_t* counts) {
+  const char* const what = "kano_k8s_pair_verdicts";
+  if (!eg || !in) return -EINVAL;
+  const std::string w(what);
+  kano_ctx* ctx = eg;
+  if (eg->device != in->device) return fail(eg, -EINVAL, w + ": contexts on two devices");
+  KCHK(hipSetDevice(eg->device));
+  KTRY(conn_source(eg, eg, what));
+  KTRY(conn_source(in, eg, what));
+  const i64 n = eg->n;
+  if (in->n != n) return fail(eg, -EINVAL, w + ": the two contexts must hold the same pods");
+  KTRY(conn_nids(eg, in, eg, what, nids_e, nids_i));
+  if (Q < 0) return fail(eg, -EINVAL, w + ": Q < 0");
+  if (Q > 0 && (!pairs || !verdict)) return fail(eg, -EINVAL, w + ": pairs or verdict is NULL");
+  kano_ctx* const src[2] = {eg, in};
+  const uint32_t* const code[2] = {code_e, code_i};
+  const uint32_t np[2] = {np_level_e, np_level_i};
+  const i64 nids[2] = {nids_e, nids_i};
+  int32_t* const dec_out[2] = {decider_e, decider_i};
+  int32_t* const pas_out[2] = {passed_e, passed_i};
+  i64 live[2];
+  KTRY(tier_codes_check(eg, what, nids, code, np, live));
+  KTRY(pairs_check(eg, what, Q, pairs, n, n));
+  KTRY(conn_sync(eg, in, eg, what));
+  eg->kpair_ms = 0.f;
+  if (counts) std::fill(counts, counts + 18, (int64_t)0);
+  if (Q == 0 || n == 0) return 0;
+  const bool has[2] = {conn_classes(eg), conn_classes(in)};
+  const size_t b_ids = sizeof(int32_t) * (size_t)Q;
+  DBuf pr, vd, key[2], dec[2], pas[2];
+  auto run = [&]() -> int {
+    KTRY(dalloc(ctx, pr, 2 * b_ids));
+    KTRY(dalloc(ctx, vd, (size_t)Q));
+    KCHK(hipMemcpyAsync(pr.p, pairs, 2 * b_ids, hipMemcpyHostToDevice, ctx->stream));
+    K8sPairArgs a{};
+    a.pairs = P_<int32_t>(pr);
+    a.Q = Q;
+    a.self = (flags & KANO_K8S_CONN_SELF) ? 1 : 0;
+    a.verdict = P_<uint8_t>(vd);
+    i64 walk = 0;
+    for (int side = 0; side < 2; ++side) {
+      kano_ctx* s = src[side];
+      K8sPairSide& d = a.side[side];
+      const int rc = pair_tables(s, what, a.pairs, Q, d.t);
+      if (rc) return s == eg ? rc : fail(eg, rc, s->err);
+      d.np = np[side];
+      if (dec_out[side]) KTRY(dalloc(ctx, dec[side], b_ids));
+      if (pas_out[side]) KTRY(dalloc(ctx, pas[side], b_ids));
+      d.decider = dec_out[side] ? P_<int32_t>(dec[side]) : nullptr;
+      d.passed = pas_out[side] ? P_<int32_t>(pas[side]) : nullptr;
+      // a side without classes constrains nothing: no list is walked
+      if (!has[side]) {
+        d.t.rcls = nullptr;
+        continue;
+      }
+      KTRY(dalloc(ctx, key[side], sizeof(uint32_t) * (size_t)nids[side]));
+      KCHK(hipMemcpyAsync(key[side].p, code[side], sizeof(uint32_t) * (size_t)nids[side],
+                          hipMemcpyHostToDevice, ctx->stream));
+      d.t.key = P_<uint32_t>(key[side]);
+      walk += pair_mean_walk(s, d.t);
+    }
+    bool wave;
+    unsigned grid;
+    pair_shape(eg, walk, eg->kpair_form, eg->kpair_grid, Q, &wave, &grid);
+    EventPair<> tev;
+    if (eg->stage_timing) KTRY(tev.start(ctx));
+    if (wave) hipLaunchKernelGGL(k_k8s_pair_wave, dim3(grid), dim3(TPB), 0, ctx->stream, a);
+    else hipLaunchKernelGGL(k_k8s_pair_lane, dim3(grid), dim3(TPB), 0, ctx->stream, a);
+    KLAUNCH();
+    KTRY(tev.stop(ctx, &eg->kpair_ms));
+    KCHK(hipMemcpyAsync(verdict, vd.p, (size_t)Q, hipMemcpyDeviceToHost, ctx->stream));
+    for (int side = 0; side < 2; ++side) {
+      if (dec_out[side])
+        KCHK(hipMemcpyAsync(dec_out[side], dec[side].p, b_ids, hipMemcpyDeviceToHost, ctx->stream));
+      if (pas_out[side])
+        KCHK(hipMemcpyAsync(pas_out[side], pas[side].p, b_ids, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    return sync(ctx);
+  };
+  const int rc = run();
+  free_temps(ctx, rc, {&pr, &vd, &key[0], &key[1], &dec[0], &dec[1], &pas[0], &pas[1]});
+  if (rc) return rc;
+  if (counts)
+    for (i64 q = 0; q < Q; ++q) {
+      const unsigned v = verdict[q];
+      counts[0] += v & 1u;
+      counts[1] += (v >> 1) & 1u;
+      ++counts[2 + ((v >> 2) & 3u) * 2 + ((v >> 4) & 1u)];
+      ++counts[10 + ((v >> 5) & 3u) * 2 + ((v >> 7) & 1u)];
+    }
+  return 0;
+}
+
+int kano_k8s_pair_verdicts_time(kano_ctx* eg, float* ms) {
+  if (!eg || !ms) return -EINVAL;
+  *ms = eg->kpair_ms;
   return 0;
 }
 

@@ -2350,6 +2350,8 @@ int kano_create(int device, kano_ctx** out) {
         if (k == "pmgrid" && v >= 0) ctx->pmask_grid = v;
         if (k == "pvf" && v >= 0 && v <= 2) ctx->verdict_form = v;
         if (k == "pvgrid" && v >= 0) ctx->verdict_grid = v;
+        if (k == "kpf" && v >= 0 && v <= 2) ctx->kpair_form = v;
+        if (k == "kpgrid" && v >= 0) ctx->kpair_grid = v;
         if (k == "dgrid" && v >= 0) ctx->diff_grid = v;
         if (k == "ggrid" && v >= 0) ctx->group_grid = v;
         if (k == "gbatch" && v >= 0) ctx->group_batches = v;
@@ -3927,10 +3929,18 @@ int pair_tables(kano_ctx* ctx, const char* what, const int32_t* pairs_dev, i64 Q
   return 0;
 }
 
+i64 pair_mean_walk(const kano_ctx* ctx, const PairTables& t) {
+  const i64 U = ctx->rc.U;
+  return (t.rcls ? (ctx->nnz_sel + U - 1) / U : 0) + t.A;
+}
+
 void pair_shape(const kano_ctx* ctx, const PairTables& t, int form_knob, int grid_knob, i64 Q,
                 bool* wave, unsigned* grid) {
-  const i64 U = ctx->rc.U;
-  const i64 sbar = (t.rcls ? (ctx->nnz_sel + U - 1) / U : 0) + t.A;
+  pair_shape(ctx, pair_mean_walk(ctx, t), form_knob, grid_knob, Q, wave, grid);
+}
+
+void pair_shape(const kano_ctx* ctx, i64 sbar, int form_knob, int grid_knob, i64 Q, bool* wave,
+                unsigned* grid) {
   *wave = form_knob ? form_knob == 2 : sbar > PAIR_WAVE_MIN;
   const i64 cap = grid_knob > 0 ? grid_knob : (i64)std::max(1, ctx->num_cus) * 8;
   *grid = (unsigned)std::min<i64>(cap, *wave ? (Q + WPB - 1) / WPB : nblk(Q));

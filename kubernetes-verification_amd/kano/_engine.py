@@ -277,6 +277,36 @@ class DeviceBuild:
         self._chk(self.lib.kano_k8s_conn_time(self.ctx, byref(ms)), "kano_k8s_conn_time")
         return float(ms.value)
 
+    def k8s_pair_verdicts(self, ing: "DeviceBuild", pairs, allow_self: bool, code_e,
+                          np_level_e: int, code_i, np_level_i: int) -> dict:
+        """Which tier and entry decide each (src, dst) of ``pairs`` under the
+        rule of k8s_conn_tiers_from (kano_k8s_pair_verdicts); this context is
+        the egress build, ``ing`` the ingress build, codes and levels as
+        there.  ``verdict`` (uint8: bit 0 allowed, 1 self, 2-3 egress tier,
+        4 egress denies, 5-6 ingress tier, 7 ingress denies), per direction
+        ``decider_*`` / ``passed_*`` (int32 engine ids, -1: none) and
+        ``counts`` (int64[18])."""
+        pairs, Q = _as_pairs(pairs)
+        ce = np.ascontiguousarray(np.asarray(code_e).reshape(-1), dtype=np.uint32)
+        ci = np.ascontiguousarray(np.asarray(code_i).reshape(-1), dtype=np.uint32)
+        verdict = np.zeros(Q, dtype=np.uint8)
+        ids = {k: np.full(Q, -1, dtype=np.int32)
+               for k in ("decider_e", "passed_e", "decider_i", "passed_i")}
+        counts = np.zeros(18, dtype=np.int64)
+        self._chk(self.lib.kano_k8s_pair_verdicts(
+            self.ctx, ing.ctx, 1 if allow_self else 0, Q, _ptr(pairs), int(ce.shape[0]), _ptr(ce),
+            int(np_level_e), int(ci.shape[0]), _ptr(ci), int(np_level_i), _ptr(verdict),
+            _ptr(ids["decider_e"]), _ptr(ids["passed_e"]), _ptr(ids["decider_i"]),
+            _ptr(ids["passed_i"]), _ptr(counts)), "kano_k8s_pair_verdicts")
+        return dict(pairs=pairs, verdict=verdict, counts=counts, **ids)
+
+    def k8s_pair_verdicts_time(self) -> float:
+        """The last k8s_pair_verdicts' device time (ms; KANO_TUNE=timing=1)."""
+        ms = ctypes.c_float(0.0)
+        self._chk(self.lib.kano_k8s_pair_verdicts_time(self.ctx, byref(ms)),
+                  "kano_k8s_pair_verdicts_time")
+        return float(ms.value)
+
     def path_shard_words(self) -> int:
         w = c_int64(0)
         self._chk(self.lib.kano_path_shard_words(self.ctx, byref(w)), "kano_path_shard_words")

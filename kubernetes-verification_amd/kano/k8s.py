@@ -446,11 +446,14 @@ def build(pods: List[Pod], policies: List[NetworkPolicy], namespaces: List[Names
 # ``namedPort`` never matches, no ``ports`` counts for every port.  Equal
 # priorities (undefined upstream) fall back to the position in ``admin``.
 #
+# ``K8sConnectivity.explain`` says for one pair which tier and rule decided
+# each direction; ``pair_verdicts`` says it for millions of pairs a call, on the
+# device (kano_k8s_pair_verdicts), with or without admin tiers.
+#
 # Out of scope: named ports (a string ``port`` / ``namedPort`` never matches a
 # numeric query), ipBlock reachability and the ``nodes`` / ``networks`` /
-# ``domainNames`` peers (the matrix is pod to pod), host-network pods, sources
-# with incremental updates (the two builds are made here, once) and a bulk
-# per-pair verdict call (``explain`` resolves one pair on the host).
+# ``domainNames`` peers (the matrix is pod to pod), host-network pods and sources
+# with incremental updates (the two builds are made here, once).
 # ---------------------------------------------------------------------------
 
 _CONF_OPS = {"In": In, "NotIn": NotIn, "Exists": Exists, "DoesNotExist": DoesNotExist}
@@ -924,6 +927,125 @@ class K8sConnectivity:
                 out["blocked_by"].append(direction)
         out["allowed"] = out["self"] or not out["blocked_by"]
         return out
+
+    def pair_verdicts(self, pairs) -> "K8sPairVerdicts":
+        """explain for many pairs at once: for every (src, dst) of ``pairs``
+        (a (Q, 2) integer array or a list of tuples; any order, duplicates
+        are fine) which tier and which rule decide each direction on this
+        object's port, resolved on the device from the two resident builds
+        and the port's codes (kano_k8s_pair_verdicts; one launch, millions of
+        pairs a call).  Works with and without AdminNetworkPolicy tiers, and
+        -- reading only the two full builds -- answers any pair of an object
+        made with ``rows=``."""
+        from ._engine import _as_pairs
+        c = self._compiled
+        n = len(c.containers)
+        pr, Q = _as_pairs(pairs)
+        if Q and (pr.min() < 0 or pr.max() >= n):
+            raise IndexError("bitarray index out of range")
+        code_e, code_i = c.codes(self.port)
+        r = self.egress.engine.k8s_pair_verdicts(self.ingress.engine, pr, self.allow_self, code_e,
+                                                 c.np_level[0], code_i, c.np_level[1])
+        policies = self._policies if c.tiered else {"network": self._policies}
+        return K8sPairVerdicts(r, c, policies)
+
+
+TIERS = ("default", "admin", "network", "baseline")
+_COUNT_KEYS = ("allowed", "self") + tuple(
+    f"{d}_{t}_{v}" for d in ("egress", "ingress") for t in TIERS for v in ("allow", "deny"))
+
+
+class K8sPairVerdicts:
+    """K8sConnectivity.pair_verdicts' result, arrays over the Q queried pairs:
+    ``pairs`` (int32 (Q, 2): src, dst), ``allowed``, ``self_`` (bool) and per
+    direction -- ``egress`` (subject src, peer dst) and ``ingress`` (subject
+    dst, peer src) -- a K8sPairDirection.  ``counts``: the pairs allowed, the
+    self pairs, and per direction, tier and verdict the pairs decided there
+    (``egress_admin_deny``, ...)."""
+
+    #: the names of the values of ``tier``
+    TIERS = TIERS
+
+    def __init__(self, r, compiled, policies):
+        v = r["verdict"]
+        self.pairs = r["pairs"]
+        self.allowed = (v & 1).astype(bool)
+        self.self_ = (v >> 1 & 1).astype(bool)
+        self.egress = K8sPairDirection(v >> 2 & 3, (v >> 4 & 1).astype(bool), r["decider_e"],
+                                       r["passed_e"], compiled.origin_egress,
+                                       compiled.tiers_egress, policies)
+        self.ingress = K8sPairDirection(v >> 5 & 3, (v >> 7 & 1).astype(bool), r["decider_i"],
+                                        r["passed_i"], compiled.origin_ingress,
+                                        compiled.tiers_ingress, policies)
+        self.counts = dict(zip(_COUNT_KEYS, map(int, r["counts"])))
+
+    def __len__(self):
+        return len(self.allowed)
+
+    def _direction(self, direction) -> "K8sPairDirection":
+        if direction not in ("egress", "ingress"):
+            raise ValueError(f"direction must be 'egress' or 'ingress', not {direction!r}")
+        return getattr(self, direction)
+
+    def _index(self, q) -> int:
+        q = int(q)
+        if not -len(self) <= q < len(self):
+            raise IndexError("pair index out of range")
+        return q
+
+    def blocked_by(self, q: int) -> List[str]:
+        """The directions that deny queried pair q (explain's ``blocked_by``;
+        a self pair may be allowed all the same)."""
+        q = self._index(q)
+        return [d for d in ("egress", "ingress") if getattr(self, d).deny[q]]
+
+    def name(self, direction: str, q: int):
+        """The rule that decided ``direction`` of queried pair q: (kind, policy
+        name, rule index, peer index, action) as explain's ``decider``, or
+        None (the default tier, or a NetworkPolicy tier that denies)."""
+        return self._direction(direction)._name("decider", self._index(q))
+
+    def passed_name(self, direction: str, q: int):
+        """The Pass rule that handed queried pair q down, named like a decider,
+        or None."""
+        return self._direction(direction)._name("passed", self._index(q))
+
+    def blame(self, direction: str, deny_only: bool = True) -> Dict[tuple, int]:
+        """{(kind, policy name, rule index): the queried pairs that rule
+        decided} in ``direction``; ``deny_only``: over the denied pairs only.
+        (A NetworkPolicy tier that denies has no deciding rule.)"""
+        d = self._direction(direction)
+        ids = d.decider[d.deny] if deny_only else d.decider
+        per_id = np.bincount(ids[ids >= 0], minlength=len(d._origin))
+        out: Dict[tuple, int] = {}
+        for p in np.flatnonzero(per_id):
+            key = d.entry(int(p))[:3]
+            out[key] = out.get(key, 0) + int(per_id[p])
+        return out
+
+
+class K8sPairDirection:
+    """One direction of K8sPairVerdicts: ``tier`` (uint8, an index into TIERS),
+    ``deny`` (bool), ``decider`` and ``passed`` (int32: entries of the
+    direction's build, -1 where there is none)."""
+
+    def __init__(self, tier, deny, decider, passed, origin, tiers, policies):
+        self.tier, self.deny, self.decider, self.passed = tier, deny, decider, passed
+        self._origin, self._tiers, self._policies = origin, tiers, policies
+
+    def tier_name(self, q: int) -> str:
+        """The name of queried pair q's tier."""
+        return TIERS[int(self.tier[q])]
+
+    def entry(self, p: int):
+        """(kind, policy name, rule index, peer index, action) of entry p of
+        the direction's build."""
+        kind, org = self._tiers[p][0], self._origin[p]
+        return kind, self._policies[kind][org[0]].name, org[2], org[3], self._tiers[p][2]
+
+    def _name(self, what: str, q: int):
+        p = int(getattr(self, what)[q])
+        return None if p < 0 else self.entry(p)
 
 
 def _connect(egress, ingress, compiled, policies, port, allow_self, isolated, device, rows,

@@ -9,7 +9,12 @@ Usage: python scripts/k8s_bench.py [--pods 10000 100000] [--reps 3]
        kano.k8s.connectivity, over the same cluster)
        python scripts/k8s_bench.py --conn --admin 50 --baseline ...   (the same
        with 50 generated AdminNetworkPolicies and a default-deny baseline: the
-       tiered call's times next to the plain call's of the same run)"""
+       tiered call's times next to the plain call's of the same run)
+       python scripts/k8s_bench.py --conn --pairs 1000000 [--admin 50 --baseline]
+       (K8sConnectivity.pair_verdicts' call, kano_k8s_pair_verdicts, on that
+       many random pairs: wall and device time, the lane and the wave form
+       forced, and beside them the device time of one kano_pair_verdicts on
+       each of the two builds -- a call that walks one list per pair)"""
 import argparse
 import json
 import os
@@ -97,6 +102,60 @@ def admin_policies(K, baseline, nns, seed=1):
     return admin, base
 
 
+def pair_times(args, n, te, ti, codes, np_level):
+    """--pairs: one kano_k8s_pair_verdicts on args.pairs random pairs over the
+    builds of the tables te / ti -- as the engine picks the form, then the lane
+    and the wave form forced (kpf=1 / 2; KANO_TUNE is read when a context is
+    created, so each form gets builds of its own) -- and one kano_pair_verdicts
+    on each build for the same pairs (all-allow tiers of one priority; the
+    ingress build with the pairs reversed, as the new call reads it).  The
+    best device time of args.reps calls each."""
+    from kano._engine import DeviceBuild
+    Q = args.pairs
+    pr = np.random.default_rng(2).integers(0, n, size=(Q, 2), dtype=np.int32)
+    rev = np.ascontiguousarray(pr[:, ::-1])
+    tune = os.environ.get("KANO_TUNE", "")
+    out = {"pairs": Q}
+    for form, knob in (("auto", ""), ("lane", "kpf=1"), ("wave", "kpf=2")):
+        os.environ["KANO_TUNE"] = ",".join(x for x in (tune, knob) if x)
+        eg, ing = DeviceBuild(te, build=False), DeviceBuild(ti, build=False)
+        eg.build_classes()
+        ing.build_classes()
+        wall = dev = None
+        for _ in range(args.reps + 1):                     # (the first call warms up)
+            t = time.perf_counter()
+            r = eg.k8s_pair_verdicts(ing, pr, True, codes[0], np_level[0], codes[1], np_level[1])
+            w, d = time.perf_counter() - t, eg.k8s_pair_verdicts_time()
+            if _ and (dev is None or d < dev):
+                wall, dev = w, d
+        out[form] = {"wall_ms": round(wall * 1e3, 3), "device_ms": round(dev, 4),
+                     "pairs_per_s": round(Q / (dev * 1e-3)) if dev > 0 else None}
+        if form == "auto":
+            out["allowed"] = int(r["counts"][0])
+            ie, ii = eg.info(), ing.info()
+            out["mean_list"] = [round(ie["NNZ_SEL"] / max(1, ie["U"]), 2),
+                                round(ii["NNZ_SEL"] / max(1, ii["U"]), 2)]
+            # the yardstick: the existing single-build call, one list per pair
+            for name, b, q in (("egress", eg, pr), ("ingress", ing, rev)):
+                P = b.info()["P"]
+                best = None
+                if P:
+                    z = np.zeros(P, dtype=np.int32)
+                    for _ in range(args.reps + 1):
+                        b.pair_verdicts(q, z, z.astype(np.uint8))
+                        d = b.pair_verdicts_time()
+                        best = d if _ and (best is None or d < best) else best
+                out[f"pair_verdicts_{name}_device_ms"] = None if best is None else round(best, 4)
+        del eg, ing
+    os.environ["KANO_TUNE"] = tune
+    both = [out[f"pair_verdicts_{k}_device_ms"] or 0.0 for k in ("egress", "ingress")]
+    out["yardstick_sum_device_ms"] = round(sum(both), 4)
+    for form in ("auto", "lane", "wave"):
+        out[form]["ratio_to_yardstick_sum"] = (round(out[form]["device_ms"] / sum(both), 3)
+                                               if sum(both) > 0 else None)
+    return out
+
+
 def conn_tiers(args, n, pods, pols, nss, rows):
     """The tiered call (kano_k8s_conn_tiers) over the builds of the same
     cluster with the generated admin and baseline policies compiled in."""
@@ -127,7 +186,10 @@ def conn_tiers(args, n, pods, pols, nss, rows):
         ie, ii = eg.info(), ing.info()
         del eg, ing
     kinds = [t[0] for t in c.tiers_egress + c.tiers_ingress]
-    return {"admin_policies": len(admin), "baseline": base is not None,
+    pairs = {}
+    if args.pairs > 0:
+        pairs = {"pair_verdicts": pair_times(args, n, te, ti, code, c.np_level)}
+    return {**pairs, "admin_policies": len(admin), "baseline": base is not None,
             "admin_entries": kinds.count("admin"), "baseline_entries": kinds.count("baseline"),
             "admin_levels": list(c.np_level), "admin_priority_ties": c.admin_priority_ties,
             "egress_entries": len(c.egress), "ingress_entries": len(c.ingress),
@@ -187,8 +249,10 @@ def conn(args):
         from kano import algorithm as alg
         em = k8s._wrap(out, n)
         tiers = {}
+        if args.pairs > 0:
+            tiers["pair_verdicts"] = pair_times(args, n, te, ti, c.codes(None), c.np_level)
         if args.admin > 0 or args.baseline:
-            tiers = {"tiers": conn_tiers(args, n, pods, pols, nss, rows)}
+            tiers["tiers"] = conn_tiers(args, n, pods, pols, nss, rows)
         print(json.dumps({
             "workload": "k8s.connectivity (conformant reading), synthetic K8s cluster",
             "form": args.conn_form,
@@ -219,6 +283,9 @@ def main():
                          "AdminNetworkPolicies")
     ap.add_argument("--baseline", action="store_true",
                     help="--conn: ... and a default-deny BaselineAdminNetworkPolicy")
+    ap.add_argument("--pairs", type=int, default=0,
+                    help="--conn: also time K8sConnectivity.pair_verdicts' call on this many "
+                         "random pairs (with --admin / --baseline: over the tiered builds too)")
     ap.add_argument("--pods", type=int, nargs="+", default=[10000, 100000])
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--form", default="classes", choices=["classes", "pods"])
