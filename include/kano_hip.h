@@ -1081,6 +1081,11 @@ int  kano_group_exchange_timing(kano_group* g, int enable, double* out /* 3 */, 
 int  kano_host_alloc(size_t bytes, void** out);
 void kano_host_free(void* p);
 
+/* The device memory the engine's buffers hold in this process, every context
+ * and every call in progress together: the bytes and the number of buffers
+ * (either may be NULL).  A destroyed context and a returned call hold none. */
+int  kano_device_bytes(int64_t* bytes, int64_t* buffers);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,7 @@
 #include <hip/hip_ext.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <functional>
 #include <cerrno>
@@ -24,6 +25,8 @@
 #include <dlfcn.h>
 #include <link.h>
 #include <thread>
+#include <type_traits>
+#include <utility>
 
 #include "kano_hip.h"
 #include "kano_internal.hpp"
@@ -56,9 +59,61 @@ constexpr int MFMA_KMIN = 8;    // min policy blocks (64 policies each) per MFMA
 
 }  // namespace
 
+// Device bytes held by DBufs and the DBufs that hold any (kano_device_bytes):
+// raised where dalloc hands a DBuf its allocation, lowered in DBuf::reset
+inline std::atomic<int64_t> g_dbuf_bytes{0}, g_dbuf_count{0};
+
+// A device allocation and its one owner: filled by dalloc, freed with whatever
+// holds it (a context member at delete ctx, a call's local at every return),
+// handed over by moving.  hipFree waits for the device, so a buffer freed on
+// a failing path has nothing in flight on it.
 struct DBuf {
   void* p = nullptr;
   size_t bytes = 0;
+  DBuf() = default;
+  DBuf(const DBuf&) = delete;
+  DBuf& operator=(const DBuf&) = delete;
+  DBuf(DBuf&& o) noexcept : p(o.p), bytes(o.bytes) {
+    o.p = nullptr;
+    o.bytes = 0;
+  }
+  DBuf& operator=(DBuf&& o) noexcept {
+    if (this != &o) {
+      (void)reset();
+      std::swap(p, o.p);
+      std::swap(bytes, o.bytes);
+    }
+    return *this;
+  }
+  ~DBuf() { (void)reset(); }
+  hipError_t reset() {
+    if (!p) return hipSuccess;
+    g_dbuf_bytes -= (int64_t)bytes;
+    --g_dbuf_count;
+    void* q = p;
+    p = nullptr;
+    bytes = 0;
+    return hipFree(q);
+  }
+};
+static_assert(!std::is_copy_constructible<DBuf>::value &&
+                  std::is_nothrow_move_constructible<DBuf>::value,
+              "a DBuf has one owner");
+
+// A page-locked host buffer and its owner
+template <typename T>
+struct Pinned {
+  T* p = nullptr;
+  Pinned() = default;
+  Pinned(const Pinned&) = delete;
+  Pinned& operator=(const Pinned&) = delete;
+  ~Pinned() {
+    if (p) (void)hipHostFree(p);
+  }
+  hipError_t alloc(size_t bytes, unsigned flags) {
+    return hipHostMalloc(reinterpret_cast<void**>(&p), bytes, flags);
+  }
+  operator T*() const { return p; }
 };
 
 struct ClassSet {
@@ -339,12 +394,12 @@ struct kano_ctx {
       shg_err;
   DBuf sizes;                // SZ_* slots: list sizes the host reads at its syncs
   DBuf icnt, ioff, sysrow, idxd;
-  u64* ghost = nullptr;      // pinned landing buffer for the size slots
+  Pinned<u64> ghost;         // pinned landing buffer for the size slots
   // pinned, coherent mirror of the size slots that the scans write directly
   // (slot-indexed): the overlapped syncs poll the host signal word the last
   // scan with host totals raises (or wait on an event when no scan does)
-  void* row_stage = nullptr;  // page-locked, ROW_STAGE_BYTES (kano_get_rows)
-  u64* gmirror = nullptr;     // SZ_SLOTS slots + the host signal word (SZ_SIGNAL)
+  Pinned<u64> row_stage;      // page-locked, ROW_STAGE_BYTES (kano_get_rows)
+  Pinned<u64> gmirror;        // SZ_SLOTS slots + the host signal word (SZ_SIGNAL)
   u64* gmirror_dev = nullptr;
   DBuf sig_ctr;              // the scans' arrival counter (one u32, zero between launches)
   u64 sig_seq = 0;           // last signal value handed to a scan
@@ -386,7 +441,6 @@ struct kano_ctx {
   hipEvent_t rows_in = nullptr;
   hipEvent_t ev_rin = nullptr;          // k_rows' inputs complete (engine stream)
   hipEvent_t ev_rin_e = nullptr;        // the same, marked by do_back's last launch
-  hipEvent_t ev_rows_end[2] = {};       // (spare)
   // set k's matrix write done: the stop event of its k_rows dispatch (a
   // separate record cost the write stream ~4.5 us between two writes)
   hipEvent_t rows_end_ev[2] = {};
@@ -416,7 +470,7 @@ struct kano_ctx {
   bool prime_alist_valid = false;  // (restored by unprime)
   u64 prime_sig = 0;               // the prologue's class-count scan's host signal
   bool prime_kept = false;         // the prologue took the kept classes (the head fill alone)
-  u64* bell = nullptr;             // page-locked, coherent; bell_dev its device address
+  Pinned<u64> bell;                // page-locked, coherent; bell_dev its device address
   u64* bell_dev = nullptr;
   u64 bell_seq = 0;
   u64 gate_ticks = 0;              // k_gate's timeout in wall-clock ticks (200 ms)
@@ -477,7 +531,6 @@ namespace kano_eng {
 int fail(kano_ctx* ctx, int code, const std::string& msg);
 int settle(kano_ctx* ctx);
 int dalloc(kano_ctx* ctx, DBuf& b, size_t bytes);
-void dfree(DBuf& b);
 int sync(kano_ctx* ctx);
 int ensure_built(kano_ctx* ctx);
 int ensure_matrix(kano_ctx* ctx);

@@ -435,8 +435,7 @@ int kano_add_policies(kano_ctx* ctx, int64_t Pn, int32_t ncols_x, const int32_t*
     KCHK(hipMemcpyAsync(P_<int32_t>(grown) + have, xval, sizeof(int32_t) * add,
                         hipMemcpyHostToDevice, ctx->stream));
     KTRY(sync(ctx));
-    dfree(ctx->xv);
-    ctx->xv = grown;
+    ctx->xv = std::move(grown);
   }
   ctx->inc_xcols += ncols_x;
   if (ncols_x > 0) ctx->cls_valid = false;   // new pod columns: the next build classifies again
@@ -454,10 +453,8 @@ int kano_add_policies(kano_ctx* ctx, int64_t Pn, int32_t ncols_x, const int32_t*
                           ctx->stream));
     }
     KTRY(sync(ctx));
-    dfree(ctx->asel);
-    dfree(ctx->aalw);
-    ctx->asel = s2;
-    ctx->aalw = a2;
+    ctx->asel = std::move(s2);
+    ctx->aalw = std::move(a2);
     ctx->inc_acap = cap;
   }
   // the batch's terms: [soff | aoff] (i64) then [scol | sval | acol | aval] (i32)
@@ -873,23 +870,16 @@ int kano_diff_pairs(kano_ctx* a, kano_ctx* b, int kind, int64_t r0, int64_t nrow
     return fail(b, -ENOSPC, "kano_diff_pairs: " + std::to_string(total) + " pairs, room for " +
                                 std::to_string(max_pairs));
   DBuf off, out;
-  auto run = [&]() -> int {
-    KTRY(dalloc(ctx, off, sizeof(i64) * (size_t)(nrows + 1 + 2 * DIFF_SCAN_TILES + 1)));
-    KTRY(dalloc(ctx, out, sizeof(int32_t) * 2 * (size_t)total));
-    i64* offp = P_<i64>(off);
-    KTRY(diff_offsets_launch(ctx, d.row + (kind ? nrows : 0), nrows, offp + nrows + 1, offp));
-    KTRY(diff_emit_launch(ctx, P_<u64>(a->M) + (r0 - a->r0) * a->ldM, a->ldM,
-                          P_<u64>(b->M) + (r0 - b->r0) * b->ldM, b->ldM, nrows, kind, r0, offp,
-                          total, P_<int32_t>(out)));
-    KCHK(hipMemcpyAsync(pairs, out.p, sizeof(int32_t) * 2 * (size_t)total, hipMemcpyDeviceToHost,
-                        ctx->stream));
-    return sync(ctx);
-  };
-  const int rc = run();
-  if (rc) (void)hipStreamSynchronize(ctx->stream);   // nothing in flight on the temporaries
-  dfree(off);
-  dfree(out);
-  return rc;
+  KTRY(dalloc(ctx, off, sizeof(i64) * (size_t)(nrows + 1 + 2 * DIFF_SCAN_TILES + 1)));
+  KTRY(dalloc(ctx, out, sizeof(int32_t) * 2 * (size_t)total));
+  i64* offp = P_<i64>(off);
+  KTRY(diff_offsets_launch(ctx, d.row + (kind ? nrows : 0), nrows, offp + nrows + 1, offp));
+  KTRY(diff_emit_launch(ctx, P_<u64>(a->M) + (r0 - a->r0) * a->ldM, a->ldM,
+                        P_<u64>(b->M) + (r0 - b->r0) * b->ldM, b->ldM, nrows, kind, r0, offp,
+                        total, P_<int32_t>(out)));
+  KCHK(hipMemcpyAsync(pairs, out.p, sizeof(int32_t) * 2 * (size_t)total, hipMemcpyDeviceToHost,
+                      ctx->stream));
+  return sync(ctx);
 }
 
 int kano_copy_matrix(kano_ctx* src, kano_ctx* dst) {
@@ -1004,43 +994,37 @@ int kano_group_counts(kano_ctx* ctx, const int32_t* gsrc, int32_t Gs, const int3
 
   // the call's own buffers
   DBuf in, masks, out, rows;
-  auto run = [&]() -> int {
-    const size_t b_gd = sizeof(int32_t) * (size_t)n, b_ord = sizeof(int32_t) * order.size(),
-                 b_run = sizeof(GroupRun) * runs.size();
-    KTRY(dalloc(ctx, in, b_gd + b_ord + b_run));
-    KTRY(dalloc(ctx, masks, sizeof(u64) * 64 * (size_t)nbp * (size_t)W));
-    KTRY(dalloc(ctx, out, sizeof(u64) * cells));
-    if (row_counts) KTRY(dalloc(ctx, rows, sizeof(int32_t) * rcells));
-    char* ip = static_cast<char*>(in.p);
-    KCHK(hipMemcpyAsync(ip, gdst, b_gd, hipMemcpyHostToDevice, ctx->stream));
-    KCHK(hipMemcpyAsync(ip + b_gd, order.data(), b_ord, hipMemcpyHostToDevice, ctx->stream));
-    KCHK(hipMemcpyAsync(ip + b_gd + b_ord, runs.data(), b_run, hipMemcpyHostToDevice,
+  const size_t b_gd = sizeof(int32_t) * (size_t)n, b_ord = sizeof(int32_t) * order.size(),
+               b_run = sizeof(GroupRun) * runs.size();
+  KTRY(dalloc(ctx, in, b_gd + b_ord + b_run));
+  KTRY(dalloc(ctx, masks, sizeof(u64) * 64 * (size_t)nbp * (size_t)W));
+  KTRY(dalloc(ctx, out, sizeof(u64) * cells));
+  if (row_counts) KTRY(dalloc(ctx, rows, sizeof(int32_t) * rcells));
+  char* ip = static_cast<char*>(in.p);
+  KCHK(hipMemcpyAsync(ip, gdst, b_gd, hipMemcpyHostToDevice, ctx->stream));
+  KCHK(hipMemcpyAsync(ip + b_gd, order.data(), b_ord, hipMemcpyHostToDevice, ctx->stream));
+  KCHK(hipMemcpyAsync(ip + b_gd + b_ord, runs.data(), b_run, hipMemcpyHostToDevice,
+                      ctx->stream));
+  // timing=1: the call's device time (the fills and the kernels, no copy)
+  EventPair<> tev;
+  if (ctx->stage_timing) KTRY(tev.start(ctx));
+  KCHK(hipMemsetAsync(out.p, 0, sizeof(u64) * cells, ctx->stream));
+  if (row_counts) KCHK(hipMemsetAsync(rows.p, 0, sizeof(int32_t) * rcells, ctx->stream));
+  const int32_t* gd_d = reinterpret_cast<const int32_t*>(ip);
+  const int32_t* ord_d = reinterpret_cast<const int32_t*>(ip + b_gd);
+  const GroupRun* run_d = reinterpret_cast<const GroupRun*>(ip + b_gd + b_ord);
+  for (i64 b0 = 0; b0 < nb; b0 += nbp) {
+    const i64 k = std::min(nbp, nb - b0);
+    KTRY(group_masks_launch(ctx, gd_d, b0, k, P_<u64>(masks)));
+    KTRY(group_rows_launch(ctx, P_<u64>(masks), b0, k, ord_d, run_d, nruns, Gd, P_<u64>(out),
+                           row_counts ? P_<int32_t>(rows) : nullptr));
+  }
+  KTRY(tev.stop(ctx, &ctx->group_ms));
+  KCHK(hipMemcpyAsync(counts, out.p, sizeof(u64) * cells, hipMemcpyDeviceToHost, ctx->stream));
+  if (row_counts)
+    KCHK(hipMemcpyAsync(row_counts, rows.p, sizeof(int32_t) * rcells, hipMemcpyDeviceToHost,
                         ctx->stream));
-    // timing=1: the call's device time (the fills and the kernels, no copy)
-    EventPair<> tev;
-    if (ctx->stage_timing) KTRY(tev.start(ctx));
-    KCHK(hipMemsetAsync(out.p, 0, sizeof(u64) * cells, ctx->stream));
-    if (row_counts) KCHK(hipMemsetAsync(rows.p, 0, sizeof(int32_t) * rcells, ctx->stream));
-    const int32_t* gd_d = reinterpret_cast<const int32_t*>(ip);
-    const int32_t* ord_d = reinterpret_cast<const int32_t*>(ip + b_gd);
-    const GroupRun* run_d = reinterpret_cast<const GroupRun*>(ip + b_gd + b_ord);
-    for (i64 b0 = 0; b0 < nb; b0 += nbp) {
-      const i64 k = std::min(nbp, nb - b0);
-      KTRY(group_masks_launch(ctx, gd_d, b0, k, P_<u64>(masks)));
-      KTRY(group_rows_launch(ctx, P_<u64>(masks), b0, k, ord_d, run_d, nruns, Gd, P_<u64>(out),
-                             row_counts ? P_<int32_t>(rows) : nullptr));
-    }
-    KTRY(tev.stop(ctx, &ctx->group_ms));
-    KCHK(hipMemcpyAsync(counts, out.p, sizeof(u64) * cells, hipMemcpyDeviceToHost, ctx->stream));
-    if (row_counts)
-      KCHK(hipMemcpyAsync(row_counts, rows.p, sizeof(int32_t) * rcells, hipMemcpyDeviceToHost,
-                          ctx->stream));
-    return sync(ctx);
-  };
-  const int rc = run();
-  if (rc) (void)hipStreamSynchronize(ctx->stream);   // nothing in flight on the temporaries
-  for (DBuf* b : {&in, &masks, &out, &rows}) dfree(*b);
-  return rc;
+  return sync(ctx);
 }
 
 int kano_group_counts_time(kano_ctx* ctx, float* ms) {
@@ -1072,18 +1056,10 @@ struct HopsStats {
 // counters and target counts; the counters' page-locked landing buffer
 struct HopsBufs {
   DBuf dist, list, bits, small, items, gath, nodes;
-  int32_t* pin = nullptr;
+  Pinned<int32_t> pin;
   EventPair<> ev;   // timing=1: a batch's bracket
   i64 B = 0;
-  float ms = 0.f;
 };
-
-void hops_free(kano_ctx* ctx, HopsBufs& h, int rc) {
-  if (rc) (void)hipStreamSynchronize(ctx->stream);   // nothing in flight on the temporaries
-  for (DBuf* b : {&h.dist, &h.list, &h.bits, &h.small, &h.items, &h.gath, &h.nodes}) dfree(*b);
-  if (h.pin) (void)hipHostFree(h.pin);
-  h.pin = nullptr;
-}
 
 // the shared preamble: arguments, the matrix present and complete, every row held
 int hops_prepare(kano_ctx* ctx, const char* what, int32_t max_hops) {
@@ -1105,8 +1081,7 @@ int hops_alloc(kano_ctx* ctx, HopsBufs& h, i64 nsrc, bool targets) {
   KTRY(dalloc(ctx, h.list, sizeof(int32_t) * (size_t)(h.B * n)));
   KTRY(dalloc(ctx, h.bits, sizeof(u64) * (size_t)((targets ? 3 : 2) * h.B * W)));
   KTRY(dalloc(ctx, h.small, sizeof(int32_t) * (size_t)(5 * h.B)));
-  KCHK(hipHostMalloc(reinterpret_cast<void**>(&h.pin), sizeof(int32_t) * (size_t)(3 * h.B),
-                     hipHostMallocDefault));
+  KCHK(h.pin.alloc(sizeof(int32_t) * (size_t)(3 * h.B), hipHostMallocDefault));
   if (ctx->stage_timing)
     for (hipEvent_t& e : h.ev.e) KCHK(hipEventCreate(&e));
   return 0;
@@ -1187,11 +1162,12 @@ int hops_batch(kano_ctx* ctx, HopsBufs& h, i64 B, const int32_t* src, int32_t ma
   return 0;
 }
 
-// closes the batch's timing (after the caller's gather / witness kernels)
+// closes the batch's timing (after the caller's gather / witness kernels):
+// hops_ms holds the batches that ended, also where a later one fails
 int hops_batch_end(kano_ctx* ctx, HopsBufs& h) {
   float ms = 0.f;
   KTRY(h.ev.stop(ctx, &ms));
-  h.ms += ms;
+  ctx->hops_ms += ms;
   return 0;
 }
 
@@ -1218,22 +1194,15 @@ int kano_hops(kano_ctx* ctx, int64_t S, const int32_t* sources, int32_t max_hops
   if (n == 0 || S == 0) return 0;
   HopsBufs h;
   HopsStats st;
-  auto run = [&]() -> int {
-    KTRY(hops_alloc(ctx, h, S, false));
-    for (i64 s0 = 0; s0 < S; s0 += h.B) {
-      const i64 B = std::min(h.B, S - s0);
-      KTRY(hops_batch(ctx, h, B, sources + s0, max_hops, nullptr, nullptr, st));
-      KTRY(hops_batch_end(ctx, h));
-      KCHK(hipMemcpyAsync(dist + s0 * n, h.dist.p, sizeof(int32_t) * (size_t)(B * n),
-                          hipMemcpyDeviceToHost, ctx->stream));
-      KTRY(sync(ctx));
-    }
-    return 0;
-  };
-  const int rc = run();
-  ctx->hops_ms = h.ms;
-  hops_free(ctx, h, rc);
-  if (rc) return rc;
+  KTRY(hops_alloc(ctx, h, S, false));
+  for (i64 s0 = 0; s0 < S; s0 += h.B) {
+    const i64 B = std::min(h.B, S - s0);
+    KTRY(hops_batch(ctx, h, B, sources + s0, max_hops, nullptr, nullptr, st));
+    KTRY(hops_batch_end(ctx, h));
+    KCHK(hipMemcpyAsync(dist + s0 * n, h.dist.p, sizeof(int32_t) * (size_t)(B * n),
+                        hipMemcpyDeviceToHost, ctx->stream));
+    KTRY(sync(ctx));
+  }
   if (info) {
     info[0] = st.levels;
     info[1] = st.rows_ored;
@@ -1259,8 +1228,10 @@ int kano_hop_pairs(kano_ctx* ctx, int64_t Q, const int32_t* pairs, int32_t max_h
       return fail(ctx, -ERANGE, "kano_hop_pairs: pod " + std::to_string(pairs[q]) +
                                     " outside [0, " + std::to_string(n) + ")");
   ctx->hops_ms = 0.f;
-  if (mode == 1) ctx->hop_total = 0;
-  if (Q == 0 || n == 0) return 0;
+  if (Q == 0 || n == 0) {
+    if (mode == 1) ctx->hop_total = 0;   // no paths, and a fetch of none is valid
+    return 0;
+  }
 
   // the pairs by source: one search per distinct source, whatever its targets
   std::vector<i64> order((size_t)Q);
@@ -1277,86 +1248,76 @@ int kano_hop_pairs(kano_ctx* ctx, int64_t Q, const int32_t* pairs, int32_t max_h
   first.push_back(Q);
   const i64 S = (i64)srcs.size();
 
-  HopsBufs h;
-  HopsStats st;
   std::vector<int32_t> sorted_nodes;  // the paths in `order`'s order
   std::vector<int32_t> dsort((size_t)Q);
-  auto run = [&]() -> int {
-    KTRY(hops_alloc(ctx, h, S, true));
-    std::vector<u64> tmask((size_t)(h.B * W));
-    std::vector<int32_t> ntgt((size_t)h.B);
-    std::vector<int2> items;
-    std::vector<HopsWitness> wit;
-    for (i64 s0 = 0; s0 < S; s0 += h.B) {
-      const i64 B = std::min(h.B, S - s0);
-      const i64 p0 = first[s0], p1 = first[s0 + B], np = p1 - p0;
-      std::fill(tmask.begin(), tmask.begin() + B * W, 0ull);
-      items.resize((size_t)np);
-      for (i64 b = 0; b < B; ++b) {
-        int32_t distinct = 0;
-        for (i64 p = first[s0 + b]; p < first[s0 + b + 1]; ++p) {
-          const int32_t t = pairs[2 * order[p] + 1];
-          u64& word = tmask[(size_t)(b * W + (t >> 6))];
-          if (!(word >> (t & 63) & 1ull)) ++distinct;
-          word |= 1ull << (t & 63);
-          items[(size_t)(p - p0)] = make_int2((int)b, t);
-        }
-        ntgt[b] = distinct;
+  HopsBufs h;   // (after the host arrays its copies land in: freed, and waited for, first)
+  HopsStats st;
+  KTRY(hops_alloc(ctx, h, S, true));
+  std::vector<u64> tmask((size_t)(h.B * W));
+  std::vector<int32_t> ntgt((size_t)h.B);
+  std::vector<int2> items;
+  std::vector<HopsWitness> wit;
+  for (i64 s0 = 0; s0 < S; s0 += h.B) {
+    const i64 B = std::min(h.B, S - s0);
+    const i64 p0 = first[s0], p1 = first[s0 + B], np = p1 - p0;
+    std::fill(tmask.begin(), tmask.begin() + B * W, 0ull);
+    items.resize((size_t)np);
+    for (i64 b = 0; b < B; ++b) {
+      int32_t distinct = 0;
+      for (i64 p = first[s0 + b]; p < first[s0 + b + 1]; ++p) {
+        const int32_t t = pairs[2 * order[p] + 1];
+        u64& word = tmask[(size_t)(b * W + (t >> 6))];
+        if (!(word >> (t & 63) & 1ull)) ++distinct;
+        word |= 1ull << (t & 63);
+        items[(size_t)(p - p0)] = make_int2((int)b, t);
       }
-      KTRY(dalloc(ctx, h.items, sizeof(int2) * (size_t)np));
-      KTRY(dalloc(ctx, h.gath, sizeof(int32_t) * (size_t)np));
-      KTRY(hops_batch(ctx, h, B, srcs.data() + s0, max_hops, tmask.data(), ntgt.data(), st));
-      KCHK(hipMemcpyAsync(h.items.p, items.data(), sizeof(int2) * (size_t)np,
-                          hipMemcpyHostToDevice, ctx->stream));
-      hipLaunchKernelGGL(k_hops_gather, dim3(nblk(np)), dim3(TPB), 0, ctx->stream,
-                         P_<int32_t>(h.dist), n, P_<int2>(h.items), np, P_<int32_t>(h.gath));
-      KLAUNCH();
-      KCHK(hipMemcpyAsync(dsort.data() + p0, h.gath.p, sizeof(int32_t) * (size_t)np,
-                          hipMemcpyDeviceToHost, ctx->stream));
-      KTRY(sync(ctx));
-      if (mode == 1) {
-        // the witnesses while the batch's dist arrays are resident
-        wit.clear();
-        i64 off = 0;
-        for (i64 p = p0; p < p1; ++p) {
-          const int32_t d = dsort[p];
-          if (d < 1) continue;
-          wit.push_back(HopsWitness{items[(size_t)(p - p0)].x, items[(size_t)(p - p0)].y, d,
-                                    pairs[2 * order[p]], off});
-          off += (i64)d + 1;
-        }
-        if (!wit.empty()) {
-          if (wit.size() > (size_t)0x7fffffff)
-            return fail(ctx, -ENOTSUP, "kano_hop_pairs: too many paths in one batch");
-          KTRY(dalloc(ctx, h.items, sizeof(HopsWitness) * wit.size()));
-          KTRY(dalloc(ctx, h.nodes, sizeof(int32_t) * (size_t)off));
-          KCHK(hipMemcpyAsync(h.items.p, wit.data(), sizeof(HopsWitness) * wit.size(),
-                              hipMemcpyHostToDevice, ctx->stream));
-          hipLaunchKernelGGL(k_hops_witness, dim3((unsigned)wit.size()), dim3(TPB), 0, ctx->stream,
-                             P_<u64>(ctx->M), ctx->ldM, n, P_<int32_t>(h.dist),
-                             P_<HopsWitness>(h.items), P_<int32_t>(h.nodes));
-          KLAUNCH();
-          KTRY(hops_batch_end(ctx, h));
-          const size_t at = sorted_nodes.size();
-          sorted_nodes.resize(at + (size_t)off);
-          KCHK(hipMemcpyAsync(sorted_nodes.data() + at, h.nodes.p, sizeof(int32_t) * (size_t)off,
-                              hipMemcpyDeviceToHost, ctx->stream));
-          KTRY(sync(ctx));
-        } else {
-          KTRY(hops_batch_end(ctx, h));
-        }
+      ntgt[b] = distinct;
+    }
+    KTRY(dalloc(ctx, h.items, sizeof(int2) * (size_t)np));
+    KTRY(dalloc(ctx, h.gath, sizeof(int32_t) * (size_t)np));
+    KTRY(hops_batch(ctx, h, B, srcs.data() + s0, max_hops, tmask.data(), ntgt.data(), st));
+    KCHK(hipMemcpyAsync(h.items.p, items.data(), sizeof(int2) * (size_t)np,
+                        hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_hops_gather, dim3(nblk(np)), dim3(TPB), 0, ctx->stream,
+                       P_<int32_t>(h.dist), n, P_<int2>(h.items), np, P_<int32_t>(h.gath));
+    KLAUNCH();
+    KCHK(hipMemcpyAsync(dsort.data() + p0, h.gath.p, sizeof(int32_t) * (size_t)np,
+                        hipMemcpyDeviceToHost, ctx->stream));
+    KTRY(sync(ctx));
+    if (mode == 1) {
+      // the witnesses while the batch's dist arrays are resident
+      wit.clear();
+      i64 off = 0;
+      for (i64 p = p0; p < p1; ++p) {
+        const int32_t d = dsort[p];
+        if (d < 1) continue;
+        wit.push_back(HopsWitness{items[(size_t)(p - p0)].x, items[(size_t)(p - p0)].y, d,
+                                  pairs[2 * order[p]], off});
+        off += (i64)d + 1;
+      }
+      if (!wit.empty()) {
+        if (wit.size() > (size_t)0x7fffffff)
+          return fail(ctx, -ENOTSUP, "kano_hop_pairs: too many paths in one batch");
+        KTRY(dalloc(ctx, h.items, sizeof(HopsWitness) * wit.size()));
+        KTRY(dalloc(ctx, h.nodes, sizeof(int32_t) * (size_t)off));
+        KCHK(hipMemcpyAsync(h.items.p, wit.data(), sizeof(HopsWitness) * wit.size(),
+                            hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(k_hops_witness, dim3((unsigned)wit.size()), dim3(TPB), 0, ctx->stream,
+                           P_<u64>(ctx->M), ctx->ldM, n, P_<int32_t>(h.dist),
+                           P_<HopsWitness>(h.items), P_<int32_t>(h.nodes));
+        KLAUNCH();
+        KTRY(hops_batch_end(ctx, h));
+        const size_t at = sorted_nodes.size();
+        sorted_nodes.resize(at + (size_t)off);
+        KCHK(hipMemcpyAsync(sorted_nodes.data() + at, h.nodes.p, sizeof(int32_t) * (size_t)off,
+                            hipMemcpyDeviceToHost, ctx->stream));
+        KTRY(sync(ctx));
       } else {
         KTRY(hops_batch_end(ctx, h));
       }
+    } else {
+      KTRY(hops_batch_end(ctx, h));
     }
-    return 0;
-  };
-  const int rc = run();
-  ctx->hops_ms = h.ms;
-  hops_free(ctx, h, rc);
-  if (rc) {
-    ctx->hop_total = -1;
-    return rc;
   }
   for (i64 p = 0; p < Q; ++p) dist[order[p]] = dsort[p];
   if (mode == 1) {
@@ -1509,47 +1470,41 @@ int kano_intents(kano_ctx* ctx, int64_t K, const uint64_t* src, const uint64_t* 
   }
 
   // the call's own buffers
-  DBuf sd, list, dd, res;
   std::vector<u64> hres((size_t)K * INTENT_RES);
-  auto run = [&]() -> int {
-    const size_t b_set = sizeof(u64) * (size_t)K * (size_t)W;
-    KTRY(dalloc(ctx, sd, 2 * b_set));
-    KTRY(dalloc(ctx, list, sizeof(int32_t) * (size_t)max_rows));
-    KTRY(dalloc(ctx, dd, sizeof(IntentDesc) * descs.size()));
-    KTRY(dalloc(ctx, res, sizeof(u64) * hres.size()));
-    u64* src_d = P_<u64>(sd);
-    u64* dst_d = src_d + (size_t)K * (size_t)W;
-    KCHK(hipMemcpyAsync(src_d, src, b_set, hipMemcpyHostToDevice, ctx->stream));
-    KCHK(hipMemcpyAsync(dst_d, dst, b_set, hipMemcpyHostToDevice, ctx->stream));
-    KCHK(hipMemcpyAsync(dd.p, descs.data(), sizeof(IntentDesc) * descs.size(),
-                        hipMemcpyHostToDevice, ctx->stream));
-    // timing=1: the call's device time (the kernels, no copy)
-    EventPair<> tev;
-    if (ctx->stage_timing) KTRY(tev.start(ctx));
-    for (i64 p = 0; p < npass; ++p) {
-      const i64 k0 = pass[p], Kp = pass[p + 1] - k0;
-      const IntentDesc* de = P_<IntentDesc>(dd) + dbase[p];
-      const i64 nitems = descs[(size_t)(dbase[p] + Kp)].ioff;
-      u64* rp = P_<u64>(res) + k0 * INTENT_RES;
-      hipLaunchKernelGGL(k_intent_lists, dim3(intent_grid(ctx, Kp)), dim3(TPB), 0, ctx->stream,
-                         src_d + k0 * W, dst_d + k0 * W, W, n, r0, r1, de, Kp,
-                         P_<int32_t>(list), rp);
-      KLAUNCH();
-      if (nitems == 0) continue;
-      hipLaunchKernelGGL(k_intent_rows, dim3(intent_grid(ctx, nitems)), dim3(TPB), 0, ctx->stream,
-                         P_<u64>(ctx->M), ctx->ldM, r0, rl, W, (const u64*)(dst_d + k0 * W), de, Kp,
-                         nitems, (const int32_t*)P_<int32_t>(list), rp);
-      KLAUNCH();
-    }
-    KTRY(tev.stop(ctx, &ctx->intents_ms));
-    KCHK(hipMemcpyAsync(hres.data(), res.p, sizeof(u64) * hres.size(), hipMemcpyDeviceToHost,
-                        ctx->stream));
-    return sync(ctx);
-  };
-  const int rc = run();
-  if (rc) (void)hipStreamSynchronize(ctx->stream);   // nothing in flight on the temporaries
-  for (DBuf* b : {&sd, &list, &dd, &res}) dfree(*b);
-  if (rc) return rc;
+  DBuf sd, list, dd, res;
+  const size_t b_set = sizeof(u64) * (size_t)K * (size_t)W;
+  KTRY(dalloc(ctx, sd, 2 * b_set));
+  KTRY(dalloc(ctx, list, sizeof(int32_t) * (size_t)max_rows));
+  KTRY(dalloc(ctx, dd, sizeof(IntentDesc) * descs.size()));
+  KTRY(dalloc(ctx, res, sizeof(u64) * hres.size()));
+  u64* src_d = P_<u64>(sd);
+  u64* dst_d = src_d + (size_t)K * (size_t)W;
+  KCHK(hipMemcpyAsync(src_d, src, b_set, hipMemcpyHostToDevice, ctx->stream));
+  KCHK(hipMemcpyAsync(dst_d, dst, b_set, hipMemcpyHostToDevice, ctx->stream));
+  KCHK(hipMemcpyAsync(dd.p, descs.data(), sizeof(IntentDesc) * descs.size(),
+                      hipMemcpyHostToDevice, ctx->stream));
+  // timing=1: the call's device time (the kernels, no copy)
+  EventPair<> tev;
+  if (ctx->stage_timing) KTRY(tev.start(ctx));
+  for (i64 p = 0; p < npass; ++p) {
+    const i64 k0 = pass[p], Kp = pass[p + 1] - k0;
+    const IntentDesc* de = P_<IntentDesc>(dd) + dbase[p];
+    const i64 nitems = descs[(size_t)(dbase[p] + Kp)].ioff;
+    u64* rp = P_<u64>(res) + k0 * INTENT_RES;
+    hipLaunchKernelGGL(k_intent_lists, dim3(intent_grid(ctx, Kp)), dim3(TPB), 0, ctx->stream,
+                       src_d + k0 * W, dst_d + k0 * W, W, n, r0, r1, de, Kp,
+                       P_<int32_t>(list), rp);
+    KLAUNCH();
+    if (nitems == 0) continue;
+    hipLaunchKernelGGL(k_intent_rows, dim3(intent_grid(ctx, nitems)), dim3(TPB), 0, ctx->stream,
+                       P_<u64>(ctx->M), ctx->ldM, r0, rl, W, (const u64*)(dst_d + k0 * W), de, Kp,
+                       nitems, (const int32_t*)P_<int32_t>(list), rp);
+    KLAUNCH();
+  }
+  KTRY(tev.stop(ctx, &ctx->intents_ms));
+  KCHK(hipMemcpyAsync(hres.data(), res.p, sizeof(u64) * hres.size(), hipMemcpyDeviceToHost,
+                      ctx->stream));
+  KTRY(sync(ctx));
   for (i64 k = 0; k < K; ++k) {
     const u64* h = hres.data() + k * INTENT_RES;
     int64_t* o = out + 6 * k;
@@ -1592,53 +1547,47 @@ int kano_intent_pairs(kano_ctx* ctx, const uint64_t* src, const uint64_t* dst, i
   std::vector<IntentDesc> desc;
   intent_descs(&ns, &flags, 1, desc);
   DBuf sd, list, dd, res, cnt, off, outb;
-  auto run = [&]() -> int {
-    KTRY(dalloc(ctx, sd, sizeof(u64) * 2 * (size_t)W));
-    KTRY(dalloc(ctx, list, sizeof(int32_t) * (size_t)ns));
-    KTRY(dalloc(ctx, dd, sizeof(IntentDesc) * 2));
-    KTRY(dalloc(ctx, res, sizeof(u64) * INTENT_RES));
-    KTRY(dalloc(ctx, cnt, sizeof(int32_t) * (size_t)ns));
-    KTRY(dalloc(ctx, off, sizeof(i64) * (size_t)(ns + 1 + 2 * DIFF_SCAN_TILES + 1)));
-    u64* src_d = P_<u64>(sd);
-    u64* dst_d = src_d + W;
-    KCHK(hipMemcpyAsync(src_d, src, sizeof(u64) * W, hipMemcpyHostToDevice, ctx->stream));
-    KCHK(hipMemcpyAsync(dst_d, dst, sizeof(u64) * W, hipMemcpyHostToDevice, ctx->stream));
-    KCHK(hipMemcpyAsync(dd.p, desc.data(), sizeof(IntentDesc) * 2, hipMemcpyHostToDevice,
-                        ctx->stream));
-    hipLaunchKernelGGL(k_intent_lists, dim3(1), dim3(TPB), 0, ctx->stream, src_d, dst_d, W, n, r0,
-                       r1, (const IntentDesc*)P_<IntentDesc>(dd), (i64)1, P_<int32_t>(list),
-                       P_<u64>(res));
-    KLAUNCH();
-    // pass one: the violations of every source row, then their offsets
-    hipLaunchKernelGGL(k_intent_row_counts, dim3(intent_grid(ctx, ns)), dim3(TPB), 0, ctx->stream,
-                       P_<u64>(ctx->M), ctx->ldM, r0, rl, W, (const u64*)dst_d, (int)flags,
-                       (const int32_t*)P_<int32_t>(list), ns, P_<int32_t>(cnt));
-    KLAUNCH();
-    i64* offp = P_<i64>(off);
-    KTRY(diff_offsets_launch(ctx, P_<int32_t>(cnt), ns, offp + ns + 1, offp));
-    i64 total = 0;
-    KCHK(hipMemcpyAsync(&total, offp + ns, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
-    KTRY(sync(ctx));
-    *count = total;
-    if (!pairs || total == 0) return 0;
-    if (total > limit)
-      return fail(ctx, -ENOSPC, "kano_intent_pairs: " + std::to_string(total) +
-                                    " pairs, room for " + std::to_string(limit));
-    // pass two: the pairs in order
-    KTRY(dalloc(ctx, outb, sizeof(int32_t) * 2 * (size_t)total));
-    hipLaunchKernelGGL(k_intent_emit, dim3(intent_grid(ctx, ns)), dim3(TPB), 0, ctx->stream,
-                       P_<u64>(ctx->M), ctx->ldM, r0, rl, W, (const u64*)dst_d, (int)flags,
-                       (const int32_t*)P_<int32_t>(list), ns, (const i64*)offp, total,
-                       P_<int32_t>(outb));
-    KLAUNCH();
-    KCHK(hipMemcpyAsync(pairs, outb.p, sizeof(int32_t) * 2 * (size_t)total, hipMemcpyDeviceToHost,
-                        ctx->stream));
-    return sync(ctx);
-  };
-  const int rc = run();
-  if (rc) (void)hipStreamSynchronize(ctx->stream);   // nothing in flight on the temporaries
-  for (DBuf* b : {&sd, &list, &dd, &res, &cnt, &off, &outb}) dfree(*b);
-  return rc;
+  KTRY(dalloc(ctx, sd, sizeof(u64) * 2 * (size_t)W));
+  KTRY(dalloc(ctx, list, sizeof(int32_t) * (size_t)ns));
+  KTRY(dalloc(ctx, dd, sizeof(IntentDesc) * 2));
+  KTRY(dalloc(ctx, res, sizeof(u64) * INTENT_RES));
+  KTRY(dalloc(ctx, cnt, sizeof(int32_t) * (size_t)ns));
+  KTRY(dalloc(ctx, off, sizeof(i64) * (size_t)(ns + 1 + 2 * DIFF_SCAN_TILES + 1)));
+  u64* src_d = P_<u64>(sd);
+  u64* dst_d = src_d + W;
+  KCHK(hipMemcpyAsync(src_d, src, sizeof(u64) * W, hipMemcpyHostToDevice, ctx->stream));
+  KCHK(hipMemcpyAsync(dst_d, dst, sizeof(u64) * W, hipMemcpyHostToDevice, ctx->stream));
+  KCHK(hipMemcpyAsync(dd.p, desc.data(), sizeof(IntentDesc) * 2, hipMemcpyHostToDevice,
+                      ctx->stream));
+  hipLaunchKernelGGL(k_intent_lists, dim3(1), dim3(TPB), 0, ctx->stream, src_d, dst_d, W, n, r0,
+                     r1, (const IntentDesc*)P_<IntentDesc>(dd), (i64)1, P_<int32_t>(list),
+                     P_<u64>(res));
+  KLAUNCH();
+  // pass one: the violations of every source row, then their offsets
+  hipLaunchKernelGGL(k_intent_row_counts, dim3(intent_grid(ctx, ns)), dim3(TPB), 0, ctx->stream,
+                     P_<u64>(ctx->M), ctx->ldM, r0, rl, W, (const u64*)dst_d, (int)flags,
+                     (const int32_t*)P_<int32_t>(list), ns, P_<int32_t>(cnt));
+  KLAUNCH();
+  i64* offp = P_<i64>(off);
+  KTRY(diff_offsets_launch(ctx, P_<int32_t>(cnt), ns, offp + ns + 1, offp));
+  i64 total = 0;
+  KCHK(hipMemcpyAsync(&total, offp + ns, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
+  KTRY(sync(ctx));
+  *count = total;
+  if (!pairs || total == 0) return 0;
+  if (total > limit)
+    return fail(ctx, -ENOSPC, "kano_intent_pairs: " + std::to_string(total) +
+                                  " pairs, room for " + std::to_string(limit));
+  // pass two: the pairs in order
+  KTRY(dalloc(ctx, outb, sizeof(int32_t) * 2 * (size_t)total));
+  hipLaunchKernelGGL(k_intent_emit, dim3(intent_grid(ctx, ns)), dim3(TPB), 0, ctx->stream,
+                     P_<u64>(ctx->M), ctx->ldM, r0, rl, W, (const u64*)dst_d, (int)flags,
+                     (const int32_t*)P_<int32_t>(list), ns, (const i64*)offp, total,
+                     P_<int32_t>(outb));
+  KLAUNCH();
+  KCHK(hipMemcpyAsync(pairs, outb.p, sizeof(int32_t) * 2 * (size_t)total, hipMemcpyDeviceToHost,
+                      ctx->stream));
+  return sync(ctx);
 }
 
 int kano_intents_time(kano_ctx* ctx, float* ms) {
@@ -1711,19 +1660,16 @@ void derived_shape(const kano_ctx* ctx, i64 ldC, int* wl, i64* cap) {
   *cap = (ctx->num_cus > 0 ? ctx->num_cus : 256) * (i64)8;
 }
 
-// a call's temporaries freed (after a failure: once nothing is in flight on them)
-void free_temps(kano_ctx* ctx, int rc, std::initializer_list<DBuf*> bufs) {
-  if (rc) (void)hipStreamSynchronize(ctx->stream);
-  for (DBuf* b : bufs) dfree(*b);
-}
-
-// the tail of a call that ran: dst's rows are new, its column results stale
-void derived_end(kano_ctx* dst, std::initializer_list<DBuf*> bufs, int rc) {
-  free_temps(dst, rc, bufs);
-  dst->cols_valid = false;
-  dst->rows_dirty = true;
-  dst->user_edited = true;
-}
+// the tail of a call that began to write dst's rows, however it ends: the rows
+// are new, the column results stale
+struct RowsEdited {
+  kano_ctx* dst;
+  ~RowsEdited() {
+    dst->cols_valid = false;
+    dst->rows_dirty = true;
+    dst->user_edited = true;
+  }
+};
 
 // The keys of the engine ids (kano_verdict.hpp: rank * 2 + action, VD_DEAD
 // for a removed id) from the raw priorities: the rank is the position among
@@ -1772,8 +1718,9 @@ int kano_policy_subset(kano_ctx* src, kano_ctx* dst, int64_t nids, const uint8_t
   }
   src->subset_ms = dst->subset_ms = 0.f;
   unsigned kept_classes = 0;
-  DBuf used, mcs, rt16, cnt;
-  auto run = [&]() -> int {
+  if (g.n > 0 && g.rl > 0) {
+    RowsEdited edited{dst};
+    DBuf used, mcs, rt16, cnt;
     KTRY(dalloc(ctx, used, (size_t)nids));
     KTRY(dalloc(ctx, cnt, sizeof(unsigned)));
     KCHK(hipMemcpyAsync(used.p, use.data(), (size_t)nids, hipMemcpyHostToDevice, ctx->stream));
@@ -1810,12 +1757,7 @@ int kano_policy_subset(kano_ctx* src, kano_ctx* dst, int64_t nids, const uint8_t
     src->subset_ms = dst->subset_ms;
     KCHK(hipMemcpyAsync(&kept_classes, cnt.p, sizeof(unsigned), hipMemcpyDeviceToHost,
                         ctx->stream));
-    return sync(ctx);
-  };
-  if (g.n > 0 && g.rl > 0) {
-    const int rc = run();
-    derived_end(dst, {&used, &mcs, &rt16, &cnt}, rc);
-    if (rc) return rc;
+    KTRY(sync(ctx));
   }
   if (info) {
     info[0] = kept_build;
@@ -1849,39 +1791,34 @@ int kano_pair_masks(kano_ctx* ctx, int64_t Q, const int32_t* pairs, int64_t nids
   }
   const bool any_dead = std::find(ctx->dead.begin(), ctx->dead.end(), 1) != ctx->dead.end();
   DBuf pr, pm, dd, od;
-  auto run = [&]() -> int {
-    const size_t b_pm = sizeof(u64) * (size_t)nids * (size_t)KW;
-    KTRY(dalloc(ctx, pr, sizeof(int32_t) * 2 * (size_t)Q));
-    KTRY(dalloc(ctx, pm, b_pm));
-    KTRY(dalloc(ctx, od, b_out));
-    if (any_dead) KTRY(dalloc(ctx, dd, (size_t)nids));
-    KCHK(hipMemcpyAsync(pr.p, pairs, sizeof(int32_t) * 2 * (size_t)Q, hipMemcpyHostToDevice,
+  const size_t b_pm = sizeof(u64) * (size_t)nids * (size_t)KW;
+  KTRY(dalloc(ctx, pr, sizeof(int32_t) * 2 * (size_t)Q));
+  KTRY(dalloc(ctx, pm, b_pm));
+  KTRY(dalloc(ctx, od, b_out));
+  if (any_dead) KTRY(dalloc(ctx, dd, (size_t)nids));
+  KCHK(hipMemcpyAsync(pr.p, pairs, sizeof(int32_t) * 2 * (size_t)Q, hipMemcpyHostToDevice,
+                      ctx->stream));
+  KCHK(hipMemcpyAsync(pm.p, pmask, b_pm, hipMemcpyHostToDevice, ctx->stream));
+  if (any_dead)
+    KCHK(hipMemcpyAsync(dd.p, ctx->dead.data(), (size_t)nids, hipMemcpyHostToDevice,
                         ctx->stream));
-    KCHK(hipMemcpyAsync(pm.p, pmask, b_pm, hipMemcpyHostToDevice, ctx->stream));
-    if (any_dead)
-      KCHK(hipMemcpyAsync(dd.p, ctx->dead.data(), (size_t)nids, hipMemcpyHostToDevice,
-                          ctx->stream));
-    PairMaskArgs a{};
-    KTRY(pair_tables(ctx, "kano_pair_masks", P_<int32_t>(pr), Q, a.t));
-    a.t.dead = any_dead ? P_<uint8_t>(dd) : nullptr;
-    a.pmask = P_<u64>(pm);
-    a.KW = KW;
-    a.out = P_<u64>(od);
-    bool wave;
-    unsigned grid;
-    pair_shape(ctx, a.t, ctx->pmask_form, ctx->pmask_grid, Q, &wave, &grid);
-    EventPair<> tev;
-    if (ctx->stage_timing) KTRY(tev.start(ctx));
-    if (wave) hipLaunchKernelGGL(k_pmask_wave, dim3(grid), dim3(TPB), 0, ctx->stream, a);
-    else hipLaunchKernelGGL(k_pmask_lane, dim3(grid), dim3(TPB), 0, ctx->stream, a);
-    KLAUNCH();
-    KTRY(tev.stop(ctx, &ctx->pmask_ms));
-    KCHK(hipMemcpyAsync(out, od.p, b_out, hipMemcpyDeviceToHost, ctx->stream));
-    return sync(ctx);
-  };
-  const int rc = run();
-  free_temps(ctx, rc, {&pr, &pm, &dd, &od});
-  return rc;
+  PairMaskArgs a{};
+  KTRY(pair_tables(ctx, "kano_pair_masks", P_<int32_t>(pr), Q, a.t));
+  a.t.dead = any_dead ? P_<uint8_t>(dd) : nullptr;
+  a.pmask = P_<u64>(pm);
+  a.KW = KW;
+  a.out = P_<u64>(od);
+  bool wave;
+  unsigned grid;
+  pair_shape(ctx, a.t, ctx->pmask_form, ctx->pmask_grid, Q, &wave, &grid);
+  EventPair<> tev;
+  if (ctx->stage_timing) KTRY(tev.start(ctx));
+  if (wave) hipLaunchKernelGGL(k_pmask_wave, dim3(grid), dim3(TPB), 0, ctx->stream, a);
+  else hipLaunchKernelGGL(k_pmask_lane, dim3(grid), dim3(TPB), 0, ctx->stream, a);
+  KLAUNCH();
+  KTRY(tev.stop(ctx, &ctx->pmask_ms));
+  KCHK(hipMemcpyAsync(out, od.p, b_out, hipMemcpyDeviceToHost, ctx->stream));
+  return sync(ctx);
 }
 
 int kano_policy_subset_time(kano_ctx* ctx, float* ms) {
@@ -1914,8 +1851,9 @@ int kano_verdict_matrix(kano_ctx* src, kano_ctx* dst, int64_t nids, const int32_
   for (i64 t = 0; t < g.A; ++t) alive_added += aflag[g.P + t] = !src->dead[g.P + t];
   src->verdict_ms = dst->verdict_ms = 0.f;
   unsigned deny_classes = 0;
-  DBuf keyd, flagd, cnt, pk, olist, okey, ocnt, vc, rt16, mrows;
-  auto run = [&]() -> int {
+  if (g.n > 0 && g.rl > 0) {
+    RowsEdited edited{dst};
+    DBuf keyd, flagd, cnt, pk, olist, okey, ocnt, vc, rt16, mrows;
     KTRY(dalloc(ctx, keyd, sizeof(uint32_t) * (size_t)nids));
     KTRY(dalloc(ctx, cnt, 2 * sizeof(u64)));   // [0]: the marked rows, [1]: the deny classes
     KCHK(hipMemcpyAsync(keyd.p, key.data(), sizeof(uint32_t) * (size_t)nids, hipMemcpyHostToDevice,
@@ -1988,12 +1926,7 @@ int kano_verdict_matrix(kano_ctx* src, kano_ctx* dst, int64_t nids, const int32_
     src->verdict_ms = dst->verdict_ms;
     KCHK(hipMemcpyAsync(&deny_classes, P_<u64>(cnt) + 1, sizeof(unsigned), hipMemcpyDeviceToHost,
                         ctx->stream));
-    return sync(ctx);
-  };
-  if (g.n > 0 && g.rl > 0) {
-    const int rc = run();
-    derived_end(dst, {&keyd, &flagd, &cnt, &pk, &olist, &okey, &ocnt, &vc, &rt16, &mrows}, rc);
-    if (rc) return rc;
+    KTRY(sync(ctx));
   }
   if (info) {
     info[0] = tally[0];
@@ -2036,38 +1969,33 @@ int kano_pair_verdicts(kano_ctx* ctx, int64_t Q, const int32_t* pairs, int64_t n
   std::vector<uint32_t> hkey((size_t)Q);
   std::vector<int32_t> hid((size_t)Q);
   DBuf pr, kd, ok, oi;
-  auto run = [&]() -> int {
-    KTRY(dalloc(ctx, pr, sizeof(int32_t) * 2 * (size_t)Q));
-    KTRY(dalloc(ctx, kd, sizeof(uint32_t) * (size_t)nids));
-    KTRY(dalloc(ctx, ok, sizeof(uint32_t) * (size_t)Q));
-    KTRY(dalloc(ctx, oi, sizeof(int32_t) * (size_t)Q));
-    KCHK(hipMemcpyAsync(pr.p, pairs, sizeof(int32_t) * 2 * (size_t)Q, hipMemcpyHostToDevice,
-                        ctx->stream));
-    KCHK(hipMemcpyAsync(kd.p, key.data(), sizeof(uint32_t) * (size_t)nids, hipMemcpyHostToDevice,
-                        ctx->stream));
-    VerdictArgs a{};
-    KTRY(pair_tables(ctx, "kano_pair_verdicts", P_<int32_t>(pr), Q, a.t));
-    a.t.key = P_<uint32_t>(kd);
-    a.out_key = P_<uint32_t>(ok);
-    a.out_id = P_<int32_t>(oi);
-    bool wave;
-    unsigned grid;
-    pair_shape(ctx, a.t, ctx->verdict_form, ctx->verdict_grid, Q, &wave, &grid);
-    EventPair<> tev;
-    if (ctx->stage_timing) KTRY(tev.start(ctx));
-    if (wave) hipLaunchKernelGGL(k_verdict_wave, dim3(grid), dim3(TPB), 0, ctx->stream, a);
-    else hipLaunchKernelGGL(k_verdict_lane, dim3(grid), dim3(TPB), 0, ctx->stream, a);
-    KLAUNCH();
-    KTRY(tev.stop(ctx, &ctx->pverdict_ms));
-    KCHK(hipMemcpyAsync(hkey.data(), ok.p, sizeof(uint32_t) * (size_t)Q, hipMemcpyDeviceToHost,
-                        ctx->stream));
-    KCHK(hipMemcpyAsync(hid.data(), oi.p, sizeof(int32_t) * (size_t)Q, hipMemcpyDeviceToHost,
-                        ctx->stream));
-    return sync(ctx);
-  };
-  const int rc = run();
-  free_temps(ctx, rc, {&pr, &kd, &ok, &oi});
-  if (rc) return rc;
+  KTRY(dalloc(ctx, pr, sizeof(int32_t) * 2 * (size_t)Q));
+  KTRY(dalloc(ctx, kd, sizeof(uint32_t) * (size_t)nids));
+  KTRY(dalloc(ctx, ok, sizeof(uint32_t) * (size_t)Q));
+  KTRY(dalloc(ctx, oi, sizeof(int32_t) * (size_t)Q));
+  KCHK(hipMemcpyAsync(pr.p, pairs, sizeof(int32_t) * 2 * (size_t)Q, hipMemcpyHostToDevice,
+                      ctx->stream));
+  KCHK(hipMemcpyAsync(kd.p, key.data(), sizeof(uint32_t) * (size_t)nids, hipMemcpyHostToDevice,
+                      ctx->stream));
+  VerdictArgs a{};
+  KTRY(pair_tables(ctx, "kano_pair_verdicts", P_<int32_t>(pr), Q, a.t));
+  a.t.key = P_<uint32_t>(kd);
+  a.out_key = P_<uint32_t>(ok);
+  a.out_id = P_<int32_t>(oi);
+  bool wave;
+  unsigned grid;
+  pair_shape(ctx, a.t, ctx->verdict_form, ctx->verdict_grid, Q, &wave, &grid);
+  EventPair<> tev;
+  if (ctx->stage_timing) KTRY(tev.start(ctx));
+  if (wave) hipLaunchKernelGGL(k_verdict_wave, dim3(grid), dim3(TPB), 0, ctx->stream, a);
+  else hipLaunchKernelGGL(k_verdict_lane, dim3(grid), dim3(TPB), 0, ctx->stream, a);
+  KLAUNCH();
+  KTRY(tev.stop(ctx, &ctx->pverdict_ms));
+  KCHK(hipMemcpyAsync(hkey.data(), ok.p, sizeof(uint32_t) * (size_t)Q, hipMemcpyDeviceToHost,
+                      ctx->stream));
+  KCHK(hipMemcpyAsync(hid.data(), oi.p, sizeof(int32_t) * (size_t)Q, hipMemcpyDeviceToHost,
+                      ctx->stream));
+  KTRY(sync(ctx));
   // the keys back to verdicts and raw priorities; a pair whose i this context
   // does not hold matched nothing and adds to no count
   for (i64 q = 0; q < Q; ++q) {
@@ -2294,9 +2222,10 @@ int kano_k8s_conn(kano_ctx* eg, kano_ctx* in, kano_ctx* dst, int flags, int64_t 
   for (i64 p = 0; p < nids_i; ++p) kept[1] += keep_i ? keep_i[p] != 0 : 1;
   unsigned long long iso[2] = {0, 0};
   dst->conn_ms = 0.f;
-  DBuf ke, ki, re, ri, cnt;
-  ConnWrite wr;
-  auto run = [&]() -> int {
+  if (n > 0 && rl > 0) {
+    RowsEdited edited{dst};
+    DBuf ke, ki, re, ri, cnt;
+    ConnWrite wr;
     const i64 Ue = eg->rc.U, ldCe = eg->ldC, Ui = in->rc.U, ldCi = in->ldC;
     KTRY(dalloc(ctx, cnt, sizeof(unsigned long long) * 2));
     if (hasE) {
@@ -2340,12 +2269,7 @@ int kano_k8s_conn(kano_ctx* eg, kano_ctx* in, kano_ctx* dst, int flags, int64_t 
                    hasI ? P_<u64>(ri) : nullptr));
     KTRY(tev.stop(ctx, &dst->conn_ms));
     KCHK(hipMemcpyAsync(iso, cnt.p, sizeof(iso), hipMemcpyDeviceToHost, ctx->stream));
-    return sync(ctx);
-  };
-  if (n > 0 && rl > 0) {
-    const int rc = run();
-    derived_end(dst, {&ke, &ki, &re, &ri, &wr.ti, &wr.xr, &cnt}, rc);
-    if (rc) return rc;
+    KTRY(sync(ctx));
   }
   if (info) {
     info[0] = (int64_t)iso[0];
@@ -2368,20 +2292,15 @@ int kano_k8s_isolated(kano_ctx* ctx, uint8_t* out) {
     return 0;
   }
   DBuf flag, cnt;
-  auto run = [&]() -> int {
-    KTRY(dalloc(ctx, flag, (size_t)n));
-    KTRY(dalloc(ctx, cnt, sizeof(unsigned long long)));
-    KCHK(hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long), ctx->stream));
-    hipLaunchKernelGGL(k_conn_isolated, dim3(nblk(n)), dim3(TPB), 0, ctx->stream,
-                       (const int32_t*)P_<int32_t>(ctx->rc.cls), (const i64*)P_<i64>(ctx->soffc),
-                       n, P_<uint8_t>(flag), P_<unsigned long long>(cnt));
-    KLAUNCH();
-    KCHK(hipMemcpyAsync(out, flag.p, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    return sync(ctx);
-  };
-  const int rc = run();
-  free_temps(ctx, rc, {&flag, &cnt});
-  return rc;
+  KTRY(dalloc(ctx, flag, (size_t)n));
+  KTRY(dalloc(ctx, cnt, sizeof(unsigned long long)));
+  KCHK(hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long), ctx->stream));
+  hipLaunchKernelGGL(k_conn_isolated, dim3(nblk(n)), dim3(TPB), 0, ctx->stream,
+                     (const int32_t*)P_<int32_t>(ctx->rc.cls), (const i64*)P_<i64>(ctx->soffc),
+                     n, P_<uint8_t>(flag), P_<unsigned long long>(cnt));
+  KLAUNCH();
+  KCHK(hipMemcpyAsync(out, flag.p, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  return sync(ctx);
 }
 
 // The tiers (k_conn_tier_*, kano_k8s_tiers.hpp): the class-level rows come
@@ -2405,9 +2324,13 @@ int kano_k8s_conn_tiers(kano_ctx* eg, kano_ctx* in, kano_ctx* dst, int flags, in
   const bool has[2] = {conn_classes(eg), conn_classes(in)};
   unsigned long long cnt_h[2] = {0, 0};
   dst->conn_ms = 0.f;
-  DBuf key[2], pk[2], olist[2], okey[2], ocnt[2], hasnp[2], r[2], flag[2], cnt;
-  ConnWrite wr;
-  auto run = [&]() -> int {
+  // a side without classes isolates nobody (also where nothing is launched)
+  for (int side = 0; side < 2; ++side)
+    if (iso_out[side] && n > 0) std::memset(iso_out[side], 0, (size_t)n);
+  if (n > 0) {
+    RowsEdited edited{dst};
+    DBuf key[2], pk[2], olist[2], okey[2], ocnt[2], hasnp[2], r[2], flag[2], cnt;
+    ConnWrite wr;
     // cnt: the isolated pods of the two sides, then k_verdict_order's scratch word
     KTRY(dalloc(ctx, cnt, sizeof(unsigned long long) * 3));
     for (int side = 0; side < 2; ++side) {
@@ -2471,18 +2394,7 @@ int kano_k8s_conn_tiers(kano_ctx* eg, kano_ctx* in, kano_ctx* dst, int flags, in
         KCHK(hipMemcpyAsync(iso_out[side], flag[side].p, (size_t)n, hipMemcpyDeviceToHost,
                             ctx->stream));
     KCHK(hipMemcpyAsync(cnt_h, cnt.p, sizeof(cnt_h), hipMemcpyDeviceToHost, ctx->stream));
-    return sync(ctx);
-  };
-  // a side without classes isolates nobody (also where nothing is launched)
-  for (int side = 0; side < 2; ++side)
-    if (iso_out[side] && n > 0) std::memset(iso_out[side], 0, (size_t)n);
-  if (n > 0) {
-    const int rc = run();
-    derived_end(dst, {&key[0], &key[1], &pk[0], &pk[1], &olist[0], &olist[1], &okey[0], &okey[1],
-                      &ocnt[0], &ocnt[1], &hasnp[0], &hasnp[1], &r[0], &r[1], &flag[0], &flag[1],
-                      &wr.ti, &wr.xr, &cnt},
-                rc);
-    if (rc) return rc;
+    KTRY(sync(ctx));
   }
   if (info) {
     info[0] = (int64_t)cnt_h[0];
@@ -2537,58 +2449,53 @@ int kano_k8s_pair_verdicts(kano_ctx* eg, kano_ctx* in, int flags, int64_t Q, con
   const bool has[2] = {conn_classes(eg), conn_classes(in)};
   const size_t b_ids = sizeof(int32_t) * (size_t)Q;
   DBuf pr, vd, key[2], dec[2], pas[2];
-  auto run = [&]() -> int {
-    KTRY(dalloc(ctx, pr, 2 * b_ids));
-    KTRY(dalloc(ctx, vd, (size_t)Q));
-    KCHK(hipMemcpyAsync(pr.p, pairs, 2 * b_ids, hipMemcpyHostToDevice, ctx->stream));
-    K8sPairArgs a{};
-    a.pairs = P_<int32_t>(pr);
-    a.Q = Q;
-    a.self = (flags & KANO_K8S_CONN_SELF) ? 1 : 0;
-    a.verdict = P_<uint8_t>(vd);
-    i64 walk = 0;
-    for (int side = 0; side < 2; ++side) {
-      kano_ctx* s = src[side];
-      K8sPairSide& d = a.side[side];
-      const int rc = pair_tables(s, what, a.pairs, Q, d.t);
-      if (rc) return s == eg ? rc : fail(eg, rc, s->err);
-      d.np = np[side];
-      if (dec_out[side]) KTRY(dalloc(ctx, dec[side], b_ids));
-      if (pas_out[side]) KTRY(dalloc(ctx, pas[side], b_ids));
-      d.decider = dec_out[side] ? P_<int32_t>(dec[side]) : nullptr;
-      d.passed = pas_out[side] ? P_<int32_t>(pas[side]) : nullptr;
-      // a side without classes constrains nothing: no list is walked
-      if (!has[side]) {
-        d.t.rcls = nullptr;
-        continue;
-      }
-      KTRY(dalloc(ctx, key[side], sizeof(uint32_t) * (size_t)nids[side]));
-      KCHK(hipMemcpyAsync(key[side].p, code[side], sizeof(uint32_t) * (size_t)nids[side],
-                          hipMemcpyHostToDevice, ctx->stream));
-      d.t.key = P_<uint32_t>(key[side]);
-      walk += pair_mean_walk(s, d.t);
+  KTRY(dalloc(ctx, pr, 2 * b_ids));
+  KTRY(dalloc(ctx, vd, (size_t)Q));
+  KCHK(hipMemcpyAsync(pr.p, pairs, 2 * b_ids, hipMemcpyHostToDevice, ctx->stream));
+  K8sPairArgs a{};
+  a.pairs = P_<int32_t>(pr);
+  a.Q = Q;
+  a.self = (flags & KANO_K8S_CONN_SELF) ? 1 : 0;
+  a.verdict = P_<uint8_t>(vd);
+  i64 walk = 0;
+  for (int side = 0; side < 2; ++side) {
+    kano_ctx* s = src[side];
+    K8sPairSide& d = a.side[side];
+    const int rc = pair_tables(s, what, a.pairs, Q, d.t);
+    if (rc) return s == eg ? rc : fail(eg, rc, s->err);
+    d.np = np[side];
+    if (dec_out[side]) KTRY(dalloc(ctx, dec[side], b_ids));
+    if (pas_out[side]) KTRY(dalloc(ctx, pas[side], b_ids));
+    d.decider = dec_out[side] ? P_<int32_t>(dec[side]) : nullptr;
+    d.passed = pas_out[side] ? P_<int32_t>(pas[side]) : nullptr;
+    // a side without classes constrains nothing: no list is walked
+    if (!has[side]) {
+      d.t.rcls = nullptr;
+      continue;
     }
-    bool wave;
-    unsigned grid;
-    pair_shape(eg, walk, eg->kpair_form, eg->kpair_grid, Q, &wave, &grid);
-    EventPair<> tev;
-    if (eg->stage_timing) KTRY(tev.start(ctx));
-    if (wave) hipLaunchKernelGGL(k_k8s_pair_wave, dim3(grid), dim3(TPB), 0, ctx->stream, a);
-    else hipLaunchKernelGGL(k_k8s_pair_lane, dim3(grid), dim3(TPB), 0, ctx->stream, a);
-    KLAUNCH();
-    KTRY(tev.stop(ctx, &eg->kpair_ms));
-    KCHK(hipMemcpyAsync(verdict, vd.p, (size_t)Q, hipMemcpyDeviceToHost, ctx->stream));
-    for (int side = 0; side < 2; ++side) {
-      if (dec_out[side])
-        KCHK(hipMemcpyAsync(dec_out[side], dec[side].p, b_ids, hipMemcpyDeviceToHost, ctx->stream));
-      if (pas_out[side])
-        KCHK(hipMemcpyAsync(pas_out[side], pas[side].p, b_ids, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    return sync(ctx);
-  };
-  const int rc = run();
-  free_temps(ctx, rc, {&pr, &vd, &key[0], &key[1], &dec[0], &dec[1], &pas[0], &pas[1]});
-  if (rc) return rc;
+    KTRY(dalloc(ctx, key[side], sizeof(uint32_t) * (size_t)nids[side]));
+    KCHK(hipMemcpyAsync(key[side].p, code[side], sizeof(uint32_t) * (size_t)nids[side],
+                        hipMemcpyHostToDevice, ctx->stream));
+    d.t.key = P_<uint32_t>(key[side]);
+    walk += pair_mean_walk(s, d.t);
+  }
+  bool wave;
+  unsigned grid;
+  pair_shape(eg, walk, eg->kpair_form, eg->kpair_grid, Q, &wave, &grid);
+  EventPair<> tev;
+  if (eg->stage_timing) KTRY(tev.start(ctx));
+  if (wave) hipLaunchKernelGGL(k_k8s_pair_wave, dim3(grid), dim3(TPB), 0, ctx->stream, a);
+  else hipLaunchKernelGGL(k_k8s_pair_lane, dim3(grid), dim3(TPB), 0, ctx->stream, a);
+  KLAUNCH();
+  KTRY(tev.stop(ctx, &eg->kpair_ms));
+  KCHK(hipMemcpyAsync(verdict, vd.p, (size_t)Q, hipMemcpyDeviceToHost, ctx->stream));
+  for (int side = 0; side < 2; ++side) {
+    if (dec_out[side])
+      KCHK(hipMemcpyAsync(dec_out[side], dec[side].p, b_ids, hipMemcpyDeviceToHost, ctx->stream));
+    if (pas_out[side])
+      KCHK(hipMemcpyAsync(pas_out[side], pas[side].p, b_ids, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  KTRY(sync(ctx));
   if (counts)
     for (i64 q = 0; q < Q; ++q) {
       const unsigned v = verdict[q];
@@ -2657,29 +2564,25 @@ int kano_reverse(kano_ctx* src, kano_ctx* dst, int64_t* info) {
   if (n == 0 || W == 0) return 0;
   unsigned long long bits = 0;
   i64 tiles = 0;
+  RowsEdited edited{dst};
   DBuf cnt;
-  auto run = [&]() -> int {
-    KTRY(dalloc(ctx, cnt, sizeof(unsigned long long)));
-    // timing=1: the call's device time (the fill and the kernel, no copy)
-    EventPair<> tev;
-    if (dst->stage_timing) KTRY(tev.start(ctx));
-    KCHK(hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long), ctx->stream));
-    const u64* S = P_<u64>(src->M);
-    u64* D = P_<u64>(dst->M);
-    unsigned long long* c = P_<unsigned long long>(cnt);
-    if (dst->reverse_tile == 1)        // (the forms measured against the default: DESIGN.md)
-      KTRY((reverse_launch<8, 8, false>(ctx, S, src->ldM, D, dst->ldM, n, W, c, &tiles)));
-    else if (dst->reverse_tile == 2)
-      KTRY((reverse_launch<16, 8, true>(ctx, S, src->ldM, D, dst->ldM, n, W, c, &tiles)));
-    else
-      KTRY((reverse_launch<8, 8, true>(ctx, S, src->ldM, D, dst->ldM, n, W, c, &tiles)));
-    KTRY(tev.stop(ctx, &dst->reverse_ms));
-    KCHK(hipMemcpyAsync(&bits, cnt.p, sizeof(bits), hipMemcpyDeviceToHost, ctx->stream));
-    return sync(ctx);
-  };
-  const int rc = run();
-  derived_end(dst, {&cnt}, rc);
-  if (rc) return rc;
+  KTRY(dalloc(ctx, cnt, sizeof(unsigned long long)));
+  // timing=1: the call's device time (the fill and the kernel, no copy)
+  EventPair<> tev;
+  if (dst->stage_timing) KTRY(tev.start(ctx));
+  KCHK(hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long), ctx->stream));
+  const u64* S = P_<u64>(src->M);
+  u64* D = P_<u64>(dst->M);
+  unsigned long long* c = P_<unsigned long long>(cnt);
+  if (dst->reverse_tile == 1)        // (the forms measured against the default: DESIGN.md)
+    KTRY((reverse_launch<8, 8, false>(ctx, S, src->ldM, D, dst->ldM, n, W, c, &tiles)));
+  else if (dst->reverse_tile == 2)
+    KTRY((reverse_launch<16, 8, true>(ctx, S, src->ldM, D, dst->ldM, n, W, c, &tiles)));
+  else
+    KTRY((reverse_launch<8, 8, true>(ctx, S, src->ldM, D, dst->ldM, n, W, c, &tiles)));
+  KTRY(tev.stop(ctx, &dst->reverse_ms));
+  KCHK(hipMemcpyAsync(&bits, cnt.p, sizeof(bits), hipMemcpyDeviceToHost, ctx->stream));
+  KTRY(sync(ctx));
   if (info) {
     info[0] = (int64_t)bits;
     info[1] = tiles;
@@ -2706,28 +2609,23 @@ int kano_zones(kano_ctx* a, kano_ctx* b, int32_t* label, int32_t* fan_out, int32
   const bool counts = fan_out || fan_in || cyclic;
   // the call's own buffer: [label | fan_out | fan_in] int32, then cyclic
   DBuf out;
-  auto run = [&]() -> int {
-    KTRY(dalloc(ctx, out, sizeof(int32_t) * 3 * (size_t)n + (size_t)n));
-    int32_t* lab = P_<int32_t>(out);
-    uint8_t* cyc = reinterpret_cast<uint8_t*>(lab + 3 * n);
-    // timing=1: the call's device time (the kernel, no copy)
-    EventPair<> tev;
-    if (a->stage_timing) KTRY(tev.start(ctx));
-    hipLaunchKernelGGL(k_zone_rows, dim3(nblk(n, TPB / 64)), dim3(TPB), 0, ctx->stream,
-                       (const u64*)P_<u64>(a->M), a->ldM, (const u64*)P_<u64>(b->M), b->ldM, n, W,
-                       counts ? 1 : 0, lab, lab + n, lab + 2 * n, cyc);
-    KLAUNCH();
-    KTRY(tev.stop(ctx, &a->zones_ms));
-    const size_t nb = sizeof(int32_t) * (size_t)n;
-    KCHK(hipMemcpyAsync(label, lab, nb, hipMemcpyDeviceToHost, ctx->stream));
-    if (fan_out) KCHK(hipMemcpyAsync(fan_out, lab + n, nb, hipMemcpyDeviceToHost, ctx->stream));
-    if (fan_in) KCHK(hipMemcpyAsync(fan_in, lab + 2 * n, nb, hipMemcpyDeviceToHost, ctx->stream));
-    if (cyclic) KCHK(hipMemcpyAsync(cyclic, cyc, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    return sync(ctx);
-  };
-  const int rc = run();
-  free_temps(ctx, rc, {&out});
-  if (rc) return rc;
+  KTRY(dalloc(ctx, out, sizeof(int32_t) * 3 * (size_t)n + (size_t)n));
+  int32_t* lab = P_<int32_t>(out);
+  uint8_t* cyc = reinterpret_cast<uint8_t*>(lab + 3 * n);
+  // timing=1: the call's device time (the kernel, no copy)
+  EventPair<> tev;
+  if (a->stage_timing) KTRY(tev.start(ctx));
+  hipLaunchKernelGGL(k_zone_rows, dim3(nblk(n, TPB / 64)), dim3(TPB), 0, ctx->stream,
+                     (const u64*)P_<u64>(a->M), a->ldM, (const u64*)P_<u64>(b->M), b->ldM, n, W,
+                     counts ? 1 : 0, lab, lab + n, lab + 2 * n, cyc);
+  KLAUNCH();
+  KTRY(tev.stop(ctx, &a->zones_ms));
+  const size_t nb = sizeof(int32_t) * (size_t)n;
+  KCHK(hipMemcpyAsync(label, lab, nb, hipMemcpyDeviceToHost, ctx->stream));
+  if (fan_out) KCHK(hipMemcpyAsync(fan_out, lab + n, nb, hipMemcpyDeviceToHost, ctx->stream));
+  if (fan_in) KCHK(hipMemcpyAsync(fan_in, lab + 2 * n, nb, hipMemcpyDeviceToHost, ctx->stream));
+  if (cyclic) KCHK(hipMemcpyAsync(cyclic, cyc, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  KTRY(sync(ctx));
   if (info) {
     std::vector<int32_t> s(label, label + n);
     std::sort(s.begin(), s.end());

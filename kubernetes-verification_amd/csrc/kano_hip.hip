@@ -43,9 +43,9 @@ int dalloc(kano_ctx* ctx, DBuf& b, size_t bytes) {
   if (b.p && b.bytes >= bytes) return 0;
   if (b.p) {
     KTRY(settle(ctx));    // an asynchronously completing matrix write may still use it
-    KCHK(hipFree(b.p));
-    b.p = nullptr;
-    b.bytes = 0;
+    const hipError_t e = b.reset();
+    if (e != hipSuccess)
+      return fail(ctx, -EIO, std::string("hipFree(b.p) -> ") + hipGetErrorString(e));
   }
   const hipError_t e = hipMalloc(&b.p, bytes);
   if (e != hipSuccess) {
@@ -54,15 +54,10 @@ int dalloc(kano_ctx* ctx, DBuf& b, size_t bytes) {
                                   hipGetErrorString(e));
   }
   b.bytes = bytes;
+  g_dbuf_bytes += (int64_t)bytes;
+  ++g_dbuf_count;
   return 0;
 }
-
-void dfree(DBuf& b) {
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.bytes = 0;
-}
-
 
 // A launch whose own dispatch marks ev (when given) -- a separate
 // hipEventRecord costs the stream ~4.5 us (scripts/micro/event_cost.hip).
@@ -337,7 +332,7 @@ void swap_rows_ptrs(kano_ctx* ctx, bool members) {
 // ---- pipelined calls: the next kano_verify's prologue behind a gate ------
 // (kano_set_pipeline; the fields' comment in kano_engine.hpp)
 void ring_bell(kano_ctx* ctx) {
-  if (ctx->bell) __atomic_store_n(ctx->bell, ctx->bell_seq, __ATOMIC_SEQ_CST);
+  if (ctx->bell) __atomic_store_n(ctx->bell.p, ctx->bell_seq, __ATOMIC_SEQ_CST);
 }
 
 // a primed prologue not taken by a kano_verify: open the gate, let it run
@@ -2277,6 +2272,26 @@ int group_rows_launch(kano_ctx* ctx, const u64* maskT, i64 b0, i64 nbp, const in
   return 0;
 }
 
+// The context's events, named once: kano_create makes them and kano_destroy
+// destroys them by this table (timed: made with timing -- the stage events,
+// the MFMA contraction's and the matrix write's brackets)
+struct CtxEvent {
+  hipEvent_t* ev;
+  bool timed;
+};
+std::vector<CtxEvent> ctx_events(kano_ctx* c) {
+  std::vector<CtxEvent> t;
+  for (hipEvent_t* e : {&c->ev_fork, &c->ev_sizes, &c->ev_tail, &c->ev_rin, &c->ev_rin_e,
+                        &c->ev_fork2, &c->ev_join2, &c->ev_pre, &c->ev_pre_done, &c->ev_pre_ac,
+                        &c->ev_sw, &c->ev_sw2, &c->ev_pairs})
+    t.push_back({e, false});
+  for (hipEvent_t* e : {&c->ev_m0, &c->ev_m1, &c->ev_rt[0][0], &c->ev_rt[0][1], &c->ev_rt[1][0],
+                        &c->ev_rt[1][1]})
+    t.push_back({e, true});
+  for (hipEvent_t& e : c->ev) t.push_back({&e, true});
+  return t;
+}
+
 }  // namespace kano_eng
 
 using namespace kano_eng;
@@ -2389,14 +2404,17 @@ int kano_create(int device, kano_ctx** out) {
   // stream2 at normal priority, measured neutral at C3 and slower where the
   // engine kernels are heavy: D1, C5 row shards)
   const int prio_main = prio_hi;
+  // (every failing path from here destroys what the context holds so far)
+  auto bail = [&](int rc) {
+    kano_destroy(ctx);
+    return rc;
+  };
   if (hipStreamCreateWithPriority(&ctx->stream, hipStreamNonBlocking, prio_main) != hipSuccess) {
-    delete ctx;
-    return -EIO;
+    ctx->stream = nullptr;
+    return bail(-EIO);
   }
   ctx->own_stream = true;
   mark("stream");
-  for (auto& e : ctx->ev) (void)hipEventCreate(&e);
-  mark("stage_events");
   // the staged GEMM's LDS (128 KB at 4 x 4) is above the default dynamic cap
   {
     const int lds44 = (int)(sizeof(u64) * 2 * GK_KC * (256 + 256));
@@ -2416,60 +2434,38 @@ int kano_create(int device, kano_ctx** out) {
   mark("func_attributes");
   if (hipStreamCreateWithFlags(&ctx->stream3, hipStreamNonBlocking) != hipSuccess) {
     ctx->stream3 = nullptr;
-    kano_destroy(ctx);
-    return -EIO;
+    return bail(-EIO);
   }
   // (the CU-masked write stream right after stream3: created later -- on the
   // first overlapped write -- it shared a hardware queue with the engine
   // stream and the pipelined step went 0.38 -> 0.68 ms; a lean context, for
   // builds the caller waits for, has none)
-  if (!g_create_lean) KTRY(ensure_masked_stream(ctx));
+  if (!g_create_lean) {
+    const int rc = ensure_masked_stream(ctx);
+    if (rc) return bail(rc);
+  }
   mark("write_streams");
-  if (hipStreamCreateWithPriority(&ctx->stream2, hipStreamNonBlocking, prio_main) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->ev_sizes, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->ev_tail, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->ev_rin, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->ev_rin_e, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->ev_fork2, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->ev_join2, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->ev_pre, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->ev_pre_done, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->ev_pre_ac, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->ev_sw, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->ev_sw2, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->ev_pairs, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreate(&ctx->ev_m0) != hipSuccess || hipEventCreate(&ctx->ev_m1) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->ev_rows_end[0], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->ev_rows_end[1], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreate(&ctx->ev_rt[0][0]) != hipSuccess || hipEventCreate(&ctx->ev_rt[0][1]) != hipSuccess ||
-      hipEventCreate(&ctx->ev_rt[1][0]) != hipSuccess || hipEventCreate(&ctx->ev_rt[1][1]) != hipSuccess) {
-    kano_destroy(ctx);
-    return -EIO;
-  }
+  if (hipStreamCreateWithPriority(&ctx->stream2, hipStreamNonBlocking, prio_main) != hipSuccess)
+    return bail(-EIO);
+  for (const CtxEvent& e : ctx_events(ctx))
+    if ((e.timed ? hipEventCreate(e.ev) : hipEventCreateWithFlags(e.ev, hipEventDisableTiming)) !=
+        hipSuccess)
+      return bail(-EIO);
   mark("stream2_events");
-  if (hipHostMalloc(reinterpret_cast<void**>(&ctx->ghost), sizeof(u64) * SZ_SLOTS,
-                    hipHostMallocDefault) != hipSuccess) {
-    kano_destroy(ctx);
-    return -ENOMEM;
-  }
-  if (hipHostMalloc(reinterpret_cast<void**>(&ctx->gmirror), sizeof(u64) * (SZ_SIGNAL + 1),
-                    hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess ||
+  if (ctx->ghost.alloc(sizeof(u64) * SZ_SLOTS, hipHostMallocDefault) != hipSuccess)
+    return bail(-ENOMEM);
+  if (ctx->gmirror.alloc(sizeof(u64) * (SZ_SIGNAL + 1),
+                         hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess ||
       hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->gmirror_dev), ctx->gmirror, 0) !=
-          hipSuccess) {
-    kano_destroy(ctx);
-    return -ENOMEM;
-  }
+          hipSuccess)
+    return bail(-ENOMEM);
   for (int k = 0; k <= SZ_SIGNAL; ++k) ctx->gmirror[k] = 0;
   // the pipelined prologue's bell (kano_set_pipeline): one coherent word the
   // gate kernel polls; its timeout in wall-clock ticks (200 ms)
-  if (hipHostMalloc(reinterpret_cast<void**>(&ctx->bell), 64,
-                    hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess ||
+  if (ctx->bell.alloc(64, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess ||
       hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->bell_dev), ctx->bell, 0) !=
-          hipSuccess) {
-    kano_destroy(ctx);
-    return -ENOMEM;
-  }
+          hipSuccess)
+    return bail(-ENOMEM);
   ctx->bell[0] = 0;
   {
     int khz = 0;
@@ -2480,13 +2476,11 @@ int kano_create(int device, kano_ctx** out) {
     ctx->wall_khz = (u64)khz;
   }
   // page-locked staging for short row reads (system_isolation's row)
-  if (hipHostMalloc(&ctx->row_stage, ROW_STAGE_BYTES, hipHostMallocDefault) != hipSuccess)
-    ctx->row_stage = nullptr;
+  if (ctx->row_stage.alloc(ROW_STAGE_BYTES, hipHostMallocDefault) != hipSuccess)
+    ctx->row_stage.p = nullptr;
   if (dalloc(ctx, ctx->sig_ctr, sizeof(uint32_t) * 4) != 0 ||
-      hipMemset(ctx->sig_ctr.p, 0, sizeof(uint32_t) * 4) != hipSuccess) {
-    kano_destroy(ctx);
-    return -ENOMEM;
-  }
+      hipMemset(ctx->sig_ctr.p, 0, sizeof(uint32_t) * 4) != hipSuccess)
+    return bail(-ENOMEM);
   mark("pinned_and_device_buffers");
   *out = ctx;
   return 0;
@@ -2496,75 +2490,18 @@ void kano_destroy(kano_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
   ring_bell(ctx);   // (a primed prologue's gate opens: the syncs below finish)
-  if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
-  if (ctx->stream3) (void)hipStreamSynchronize(ctx->stream3);
-  if (ctx->stream3m) (void)hipStreamSynchronize(ctx->stream3m);
-  for (hipStream_t t : {ctx->stream_x, ctx->stream2_x, ctx->stream3x, ctx->stream2_u})
+  const std::initializer_list<hipStream_t> streams = {
+      ctx->own_stream ? ctx->stream : nullptr, ctx->stream2, ctx->stream3, ctx->stream3m,
+      ctx->stream_x, ctx->stream2_x, ctx->stream3x, ctx->stream2_u};
+  if (ctx->stream && !ctx->own_stream) (void)hipStreamSynchronize(ctx->stream);   // (a caller's)
+  for (hipStream_t t : streams)
     if (t) (void)hipStreamSynchronize(t);
-  if (ctx->ghost) (void)hipHostFree(ctx->ghost);
-  if (ctx->gmirror) (void)hipHostFree(ctx->gmirror);
-  if (ctx->row_stage) (void)hipHostFree(ctx->row_stage);
-  if (ctx->bell) (void)hipHostFree(ctx->bell);
-  dfree(ctx->sizes_alt);
-  dfree(ctx->gate_wait);
-  for (ClassSet* cs : {&ctx->rc, &ctx->cc}) {
-    DBuf* b[] = {&cs->keys_d, &cs->table, &cs->smin, &cs->slot_of, &cs->flag, &cs->cid, &cs->cls,
-                 &cs->rep,    &cs->mcnt,  &cs->mcur, &cs->moff,    &cs->mem,  &cs->cval};
-    for (DBuf* x : b) dfree(*x);
-  }
-  for (SideMatch* sx : {&ctx->sm, &ctx->am}) {
-    DBuf* b[] = {&sx->toff,  &sx->tslot, &sx->tval, &sx->pmask,  &sx->moff, &sx->mslot,
-                 &sx->table, &sx->pslot, &sx->gcnt, &sx->goff,   &sx->gcur, &sx->gmem,
-                 &sx->pstart, &sx->plen, &sx->bits, &sx->bcnt,   &sx->boff};
-    for (DBuf* x : b) dfree(*x);
-  }
-  DBuf* bufs[] = {&ctx->pv,     &ctx->scnt,    &ctx->cost,    &ctx->soffc,     &ctx->scur,
-                  &ctx->slist,  &ctx->maxs,    &ctx->wicnt,   &ctx->wioff,     &ctx->hflag,
-                  &ctx->hoff,   &ctx->hlist,   &ctx->sq,      &ctx->pfoff,     &ctx->ACT,
-                  &ctx->AC,     &ctx->nca,     &ctx->acnt,    &ctx->alcoff,    &ctx->alc,
-                  &ctx->aloff,  &ctx->alist,   &ctx->M,       &ctx->Mc,        &ctx->color,
-                  &ctx->colnand, &ctx->col_and, &ctx->col_or_c, &ctx->col_nand_c, &ctx->scan_tmp, &ctx->scan_tmp2,
-                  &ctx->shg_h,  &ctx->shg_tkey, &ctx->shg_trep, &ctx->shg_slot, &ctx->shg_isrep,
-                  &ctx->shg_gidx, &ctx->shg_gid, &ctx->shg_reps, &ctx->shg_sub, &ctx->shg_err, &ctx->sig_ctr,
-                  &ctx->gid,    &ctx->cgroup,  &ctx->R,       &ctx->multi,     &ctx->A1,
-                  &ctx->A2,     &ctx->own,     &ctx->cross,   &ctx->gmin,      &ctx->gmax,
-                  &ctx->flags,  &ctx->T,       &ctx->loff,    &ctx->L,         &ctx->tp,
-                  &ctx->poff,   &ctx->out,     &ctx->conflict_out, &ctx->scratch_words, &ctx->ident, &ctx->ecls,
-                  &ctx->impact_out, &ctx->impact_ess, &ctx->diff_buf,
-                  &ctx->pp_pairs, &ctx->pp_cover, &ctx->pp_off, &ctx->pp_hist, &ctx->pp_dead,
-                  &ctx->pp_pol,
-                  &ctx->tcnt,   &ctx->toff,    &ctx->sizes,   &ctx->icnt,      &ctx->ioff,
-                  &ctx->sysrow, &ctx->wicls,   &ctx->idxd,
-                  &ctx->ckey,   &ctx->corder,  &ctx->kcnt,    &ctx->koff,
-                  &ctx->gids,
-                  &ctx->pT,     &ctx->pR[0],   &ctx->pR[1],   &ctx->pD[0],     &ctx->pD[1],
-                  &ctx->pA,     &ctx->pB,      &ctx->pcnt,
-                  &ctx->xv,     &ctx->asel,    &ctx->aalw,    &ctx->iterm,     &ctx->idead,
-                  &ctx->irows,  &ctx->xw,      &ctx->xg,
-                  &ctx->rw_items, &ctx->rw_segs, &ctx->rw_ticket, &ctx->slist_tmp,
-                  &ctx->dx_sc, &ctx->dx_sa, &ctx->mct};
-  for (DBuf* b : bufs) dfree(*b);
-  RowsInputs& ra = ctx->rin_alt;
-  for (DBuf* b : {&ra.wioff, &ra.wicls, &ra.soffc, &ra.slist, &ra.aloff, &ra.alist, &ra.alcoff,
-                  &ra.alc, &ra.rmoff, &ra.rmem, &ra.cmoff, &ra.cmem, &ra.ccls, &ra.hflag,
-                  &ra.hlist, &ra.Mc})
-    dfree(*b);
-  for (auto& e : ctx->ev)
-    if (e) (void)hipEventDestroy(e);
-  if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
-  if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
-  if (ctx->stream3) (void)hipStreamDestroy(ctx->stream3);
-  if (ctx->stream3m) (void)hipStreamDestroy(ctx->stream3m);
-  for (hipStream_t t : {ctx->stream_x, ctx->stream2_x, ctx->stream3x, ctx->stream2_u})
+  for (hipStream_t t : streams)
     if (t) (void)hipStreamDestroy(t);
-  for (hipEvent_t e : {ctx->ev_sw, ctx->ev_sw2})
-    if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : {ctx->ev_fork, ctx->ev_tail, ctx->ev_rin, ctx->ev_rin_e, ctx->ev_sizes,
-                       ctx->ev_fork2, ctx->ev_join2, ctx->ev_pre, ctx->ev_pre_done, ctx->ev_pre_ac, ctx->ev_pairs, ctx->ev_m0, ctx->ev_m1, ctx->ev_rows_end[0],
-                       ctx->ev_rows_end[1], ctx->ev_rt[0][0], ctx->ev_rt[0][1], ctx->ev_rt[1][0],
-                       ctx->ev_rt[1][1]})
-    if (e) (void)hipEventDestroy(e);
+  for (const CtxEvent& e : ctx_events(ctx))
+    if (*e.ev) (void)hipEventDestroy(*e.ev);
+  // the device and page-locked buffers free themselves, after the streams and
+  // events: every stream was synchronised above, so nothing is in flight on them
   delete ctx;
 }
 
@@ -2679,9 +2616,7 @@ int kano_set_expressions(kano_ctx* ctx, int32_t E, const int32_t* col, const int
     KLAUNCH();
   }
   KTRY(sync(ctx));
-  dfree(args);
-  dfree(ctx->pv);
-  ctx->pv = grown;
+  ctx->pv = std::move(grown);
   ctx->ncols = (int32_t)(nc + E);
   ctx->colbits.resize((size_t)ctx->ncols, 3);   // values 0 / 1 pack as 3 / 4
   ctx->have_pols = false;
@@ -3060,7 +2995,7 @@ int kano_get_rows(kano_ctx* ctx, int64_t r0, int64_t nrows, uint64_t* dst) {
   const size_t bytes = sizeof(u64) * (size_t)ctx->W * (size_t)nrows;
   const bool staged = ctx->row_stage && bytes <= ROW_STAGE_BYTES;
   const u64* src = P_<u64>(ctx->M) + (r0 - ctx->r0) * ctx->ldM;
-  void* to = staged ? ctx->row_stage : dst;
+  void* to = staged ? (void*)ctx->row_stage.p : (void*)dst;
   // (contiguous rows: a linear copy -- the first strided copy of a process
   // set up its blit kernel, ~8 ms on the first system_isolation call)
   if (nrows == 1 || ctx->ldM == ctx->W)
@@ -3080,22 +3015,17 @@ int kano_rows_digest(kano_ctx* ctx, int64_t r0, int64_t nrows, uint64_t* out) {
   if (nrows == 0) return 0;
   DBuf d;
   KTRY(dalloc(ctx, d, sizeof(u64) * (size_t)nrows));
-  int rc = 0;
-  for (i64 q = 0; q < nrows && rc == 0; q += 1 << 30) {   // grid.x limit
+  for (i64 q = 0; q < nrows; q += 1 << 30) {   // grid.x limit
     const i64 cnt = std::min<i64>(nrows - q, 1 << 30);
     hipLaunchKernelGGL(k_row_digest, dim3((unsigned)cnt), dim3(TPB), 0, ctx->stream,
                        P_<u64>(ctx->M) + (r0 - ctx->r0 + q) * ctx->ldM, ctx->ldM, ctx->W,
                        P_<u64>(d) + q);
-    if (hipGetLastError() != hipSuccess) rc = fail(ctx, -EIO, "kano_rows_digest: launch");
+    if (hipGetLastError() != hipSuccess) return fail(ctx, -EIO, "kano_rows_digest: launch");
   }
-  if (rc == 0 &&
-      hipMemcpyAsync(out, d.p, sizeof(u64) * nrows, hipMemcpyDeviceToHost, ctx->stream) !=
-          hipSuccess)
-    rc = fail(ctx, -EIO, "kano_rows_digest: copy");
-  if (rc == 0) rc = sync(ctx);
-  else (void)sync(ctx);
-  dfree(d);
-  return rc;
+  if (hipMemcpyAsync(out, d.p, sizeof(u64) * nrows, hipMemcpyDeviceToHost, ctx->stream) !=
+      hipSuccess)
+    return fail(ctx, -EIO, "kano_rows_digest: copy");
+  return sync(ctx);
 }
 
 int kano_put_rows(kano_ctx* ctx, int64_t r0, int64_t nrows, const uint64_t* src) {
@@ -4917,6 +4847,12 @@ int kano_host_alloc(size_t bytes, void** out) {
 
 void kano_host_free(void* p) {
   if (p) (void)hipHostFree(p);
+}
+
+int kano_device_bytes(int64_t* bytes, int64_t* buffers) {
+  if (bytes) *bytes = g_dbuf_bytes.load();
+  if (buffers) *buffers = g_dbuf_count.load();
+  return 0;
 }
 
 int kano_stage_times(kano_ctx* ctx, float* ms) {

@@ -162,6 +162,7 @@ SIGNATURES = {
     "kano_group_exchange_timing": (c_int, [c_void_p, c_int, c_void_p, c_int]),
     "kano_host_alloc": (c_int, [ctypes.c_size_t, POINTER(c_void_p)]),
     "kano_host_free": (None, [c_void_p]),
+    "kano_device_bytes": (c_int, [POINTER(c_int64), POINTER(c_int64)]),
 }
 
 INFO_SLOTS = 18
@@ -218,3 +219,10 @@ def gpu_available() -> bool:
         lib.kano_destroy(ctx)
         return True
     return False
+
+
+def device_bytes() -> tuple:
+    """(bytes, buffers) of device memory the engine's buffers hold in this process."""
+    b, k = c_int64(), c_int64()
+    check(None, load().kano_device_bytes(ctypes.byref(b), ctypes.byref(k)), "kano_device_bytes")
+    return b.value, k.value
