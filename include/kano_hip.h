@@ -66,7 +66,11 @@ typedef struct kano_ctx kano_ctx;
 #define KANO_INFO_HEAVY_KERNEL 16 /* 0 none, 1 k_heavy_mc_or, 2 k_heavy_mc_mfma (split K), 3 k_heavy_gemm */
 #define KANO_INFO_CLS_REUSED 17 /* builds on this context that reused the kept pod
                                   classification (see kano_set_policies)        */
-#define KANO_INFO_NSLOTS   18
+#define KANO_INFO_MATCH_FORM 18 /* how the current policies are matched to the pod
+                                  classes: bit 0 the select side takes the dense
+                                  evaluation (more than 64 distinct slot sets),
+                                  bit 1 the allow side; a clear bit: the hash join */
+#define KANO_INFO_NSLOTS   19
 
 /* Lifetime.  No reference counterpart: the reference keeps its state in
  * Python objects (kano_py/kano/model.py:167-169 ReachabilityMatrix.__init__). */

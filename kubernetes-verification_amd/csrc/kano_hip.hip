@@ -2931,6 +2931,7 @@ int kano_info(kano_ctx* ctx, int64_t* out) {
   out[KANO_INFO_WORK_ITEMS] = ctx->wi_total;
   out[KANO_INFO_ROWS_KERNEL] = ctx->rows_kernel;
   out[KANO_INFO_CLS_REUSED] = ctx->cls_reused;
+  if (ctx->have_pols) out[KANO_INFO_MATCH_FORM] = (ctx->sm.dense ? 1 : 0) | (ctx->am.dense ? 2 : 0);
   return 0;
 }
 

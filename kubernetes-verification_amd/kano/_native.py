@@ -165,10 +165,10 @@ SIGNATURES = {
     "kano_device_bytes": (c_int, [POINTER(c_int64), POINTER(c_int64)]),
 }
 
-INFO_SLOTS = 18
+INFO_SLOTS = 19
 INFO = dict(N=0, W=1, P=2, U=3, NNZ_SEL=4, NNZ_ALW=5, HEAVY=6, ROW0=7, ROW1=8, MAXSEL=9,
             UA=10, HEAVY_PATH=11, WORK_ITEMS=12, ROWS_KERNEL=13, ROWS_CUS=14,
-            HEAVY_SEL=15, HEAVY_KERNEL=16, CLS_REUSED=17)
+            HEAVY_SEL=15, HEAVY_KERNEL=16, CLS_REUSED=17, MATCH_FORM=18)
 PATHS = {"auto": 0, "bitwise": 1, "mfma": 2}
 STORED_GROUPS = -1   # KANO_STORED_GROUPS
 GROUP_LEAN, GROUP_RCCL, GROUP_COPY = 1, 2, 4   # KANO_GROUP_* flags

@@ -794,20 +794,50 @@ def _mixed_cluster(seed, n=300, P=60, nkeys=6):
     return {"label": "tenant", "pods": pods, "policies": pols}
 
 
+def _mixed_narrow(seed, n=300, P=200, nkeys=8):
+    """_mixed_cluster's pods over 8 keys; every side names 1 to 3 of them and
+    is never empty, so no policy matches every pod and the matrix is neither
+    empty nor full; 200 policies use more than 64 key sets a side (the dense
+    matching, MATCH_FORM 3)."""
+    obj = _mixed_cluster(seed, n=n, P=0, nkeys=nkeys)
+    import math
+    rng = np.random.default_rng(seed + 1000)
+    vals = [0, 1, 2, 1.0, True, "1", "a", "b", math.nan, 3, 4.5]
+    keys = [f"k{i}" for i in range(nkeys)]
+
+    def side():
+        return {str(k): vals[rng.integers(len(vals))]
+                for k in rng.choice(keys, size=rng.integers(1, 4), replace=False)}
+    obj["policies"] = [{"name": f"q{p}", "select": side(), "allow": side(),
+                        "direction": "ingress" if rng.random() < 0.5 else "egress",
+                        "protocol": ["TCP", "80"]} for p in range(P)]
+    return obj
+
+
 @pytest.mark.parametrize("packed", ["1", "0"])
-@pytest.mark.parametrize("seed", [11, 12, 13])
+@pytest.mark.parametrize("seed", [11, 12, 13, "narrow-21", "narrow-26"])
 def test_mixed_types_packed_and_unpacked(seed, packed, monkeypatch):
     """Class hashing on packed key words (value id + 3, ids >= -3 with NaN's
-    -3) and on gathered pod values give the oracle's matrix and checks."""
+    -3) and on gathered pod values give the oracle's matrix and checks.  The
+    seeds 11-13 give matrices of ones (some policies are empty on both sides);
+    the narrow family's say something, asserted from the oracle, and take the
+    dense matching."""
     from kano._engine import DeviceBuild
     from kano._intern import intern, group_ids
     from kano._bits import set_bit_indices, words_to_bool
     from oracle import kano_oracle as orc
     monkeypatch.setenv("KANO_TUNE", f"packed={packed}")
-    obj = _mixed_cluster(seed)
+    narrow = isinstance(seed, str)
+    obj = _mixed_narrow(int(seed.split("-")[1])) if narrow else _mixed_cluster(seed)
     cs, ps = api_objects(obj)
     ref = orc.run_c(obj, label="tenant")
+    if narrow:
+        bits = np.unpackbits(ref["M"].view(np.uint8), axis=1, bitorder="little")[:, :len(cs)]
+        assert 0 < int(bits.sum()) < len(cs) ** 2
+        assert ref["system_isolation"] and ref["user_crosscheck"] and ref["shadow_count"] > 0
+        assert ref["all_isolated"]
     eng = DeviceBuild(intern(cs, ps))
+    assert eng.info()["MATCH_FORM"] == (3 if narrow else 0)
     n = len(cs)
     assert np.array_equal(eng.rows(0, n), ref["M"])
     r = eng.verify(group_ids(cs, "tenant"), sys_row=0, shadow=True)
@@ -821,21 +851,26 @@ def test_mixed_types_packed_and_unpacked(seed, packed, monkeypatch):
 
 @pytest.mark.parametrize("tune", ["", "async=0", "packed=0", "shr=4"])
 @pytest.mark.parametrize("n,P", [(1, 0), (1, 1), (2, 3), (5, 1), (63, 7), (64, 64), (65, 9),
-                                 (130, 40)])
+                                 (130, 40), pytest.param(64, (64, 37), id="64-64-seed37")])
 def test_verify_small_shapes_vs_oracle(n, P, tune, monkeypatch):
     """kano_verify on tiny and word-boundary shapes (1, 63, 64, 65 pods; no
     policy; more policies than pods) with synchronous and asynchronous
     completion and both classification forms: every
     list, the pairs and the count-only count equal the C oracle's (a
-    restatement of algorithm.py:4-80)."""
+    restatement of algorithm.py:4-80).  (64, 64) at its own seed is a matrix
+    of ones; P = (64, 37) is that shape at seed 37, where it is not.)"""
     from kano._engine import DeviceBuild
     from kano._intern import intern, group_ids
     from kano.synth import make_cluster, objects_from_json
     from kano import model
     from oracle import kano_oracle as orc
     monkeypatch.setenv("KANO_TUNE", tune)
-    obj = make_cluster(n, P, "sparse", seed=n * 1000 + P).to_json_obj()
+    P, seed = P if isinstance(P, tuple) else (P, n * 1000 + P)
+    obj = make_cluster(n, P, "sparse", seed=seed).to_json_obj()
     ref = orc.run_c(obj, label="tenant")
+    if seed == 37:
+        ones = int(np.unpackbits(ref["M"].view(np.uint8), axis=1, bitorder="little")[:, :n].sum())
+        assert 0 < ones < n * n and ref["system_isolation"] and ref["user_crosscheck"]
     cs, ps = objects_from_json(obj, model)
     gid = group_ids(cs, "tenant")
     eng = DeviceBuild(intern(cs, ps), build=False)
