@@ -982,6 +982,51 @@ int kano_k8s_pair_verdicts(kano_ctx* eg, kano_ctx* in, int flags /* KANO_K8S_CON
 /* KANO_TUNE timing=1: the last kano_k8s_pair_verdicts' device time in ms on
  * eg (the kernel, no copies), else 0. */
 int kano_k8s_pair_verdicts_time(kano_ctx* eg, float* ms);
+/* K8sConnectivity.rule_usage: which entries of the two builds do anything at
+ * all, counted exactly over every ordered pair (x, y) of [0, n)^2 and per
+ * direction (subject x, peer y: egress x = src on eg, ingress x = dst on in).
+ * With flags & KANO_K8S_CONN_SELF the n pairs x == y are left out of every
+ * count (self traffic is allowed before any rule is read); without it they are
+ * resolved like any other pair.  tier, deny, decider and passed of a pair are
+ * kano_k8s_pair_verdicts' above, unchanged.  Per direction:
+ *   decided[id]  the pairs whose decider is entry id
+ *   passed[id]   the pairs whose passed entry is id
+ *   sole[g]      the pairs of tier network that are allowed where every live
+ *                entry of code np_level * 4 that selects x and allows y belongs
+ *                to group g
+ *   tiers        per tier 0..3 its (allow, deny) pairs, 8 values; egress first.
+ *                They sum to n * n, or n * n - n with the self flag.
+ * group_* (nullable, nids each): an int32 per engine id, non-decreasing in the
+ * id and from 0 on (the entries of one rule are contiguous); NULL: every id
+ * its own group.  sole_* holds last group + 1 values.
+ * decided == 0 and passed == 0: the entry is dead -- removing it changes no
+ * verdict of this query.  For a group at np_level, sole == 0 says removing its
+ * entries alone changes no verdict, and removal denies exactly sole pairs of
+ * that direction; sole[g] <= the sum of decided over g.
+ * A side without policies has no classes: its arrays are zero and the whole
+ * domain is (default, allow).  n == 0 launches nothing and returns zeros.
+ * The answer depends only on (row class of x, column class of y): one walk of
+ * every class's ordered list resolves 64 column classes a word and weights the
+ * newly decided bits by the class sizes, so the cost is that of
+ * kano_k8s_conn_tiers' class step, not of n * n pair walks.  The counters are
+ * 64-bit integer atomics: exact and independent of the order of arrival.
+ * Errors as kano_k8s_pair_verdicts (source state, nids, codes; reported on eg,
+ * both contexts stay usable); -EINVAL also for groups that decrease or start
+ * below 0.  The device buffers are the call's own, freed on return; the
+ * sources' tables and stored results are unchanged.  KANO_TUNE kugrid=K caps
+ * the class kernel's grid at K blocks. */
+int kano_k8s_rule_usage(kano_ctx* eg, kano_ctx* in, int flags /* KANO_K8S_CONN_SELF */,
+                        int64_t nids_e, const uint32_t* code_e, uint32_t np_level_e,
+                        const int32_t* group_e /* nids_e, nullable */,
+                        int64_t nids_i, const uint32_t* code_i, uint32_t np_level_i,
+                        const int32_t* group_i /* nids_i, nullable */,
+                        int64_t* decided_e, int64_t* passed_e, /* nids_e each, nullable */
+                        int64_t* sole_e /* groups of egress, nullable */,
+                        int64_t* decided_i, int64_t* passed_i, int64_t* sole_i,
+                        int64_t* tiers /* 16: egress 8, ingress 8; nullable */);
+/* KANO_TUNE timing=1: the last kano_k8s_rule_usage's device time in ms on eg
+ * (the fills and the kernels, no copies), else 0. */
+int kano_k8s_rule_usage_time(kano_ctx* eg, float* ms);
 
 /* kano_build without the matrix write (model.py:125-165 up to the class-level
  * matrix Mc, the lists and the column checks): M is written on first use

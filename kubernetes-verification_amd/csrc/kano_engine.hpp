@@ -233,6 +233,7 @@ struct kano_ctx {
   int verdict_grid = 0;      // pvgrid=K: at most K blocks for k_verdict_lane / k_verdict_wave (0: 8 per CU)
   int kpair_form = 0;        // kpf=1/2: kano_k8s_pair_verdicts' lane / wave form forced (0: by the two lists' length)
   int kpair_grid = 0;        // kpgrid=K: at most K blocks for k_k8s_pair_lane / k_k8s_pair_wave (0: 8 per CU)
+  int kusage_grid = 0;       // kugrid=K: at most K blocks for k_usage_class (0: 8 per CU)
   int diff_grid = 0;         // dgrid=K: at most K blocks for k_diff_rows (0: every resident block)
   int group_grid = 0;        // ggrid=K: at most K blocks for k_group_rows (0: every resident block)
   int group_batches = 0;     // gbatch=K: at most K batches of 64 destination groups in one
@@ -380,6 +381,9 @@ struct kano_ctx {
   // K8sConnectivity.pair_verdicts (kano_k8s_pair_verdicts, in the egress
   // context): the device buffers are the call's own; only the time stays
   float kpair_ms = 0.f;       // timing=1: the last kano_k8s_pair_verdicts' kernel
+  // K8sConnectivity.rule_usage (kano_k8s_rule_usage, in the egress context):
+  // the device buffers are the call's own; only the time stays
+  float kusage_ms = 0.f;      // timing=1: the last kano_k8s_rule_usage's fills + kernels
   // reverse_matrix / reach_zones (kano_reverse, in the destination context;
   // kano_zones, in the first): the device buffers are the call's own; only
   // the times stay

@@ -10,6 +10,7 @@
 #include "kano_k8s_conn.hpp"
 #include "kano_k8s_pairs.hpp"
 #include "kano_k8s_tiers.hpp"
+#include "kano_k8s_usage.hpp"
 #include "kano_path.hpp"
 #include "kano_hops.hpp"
 #include "kano_intents.hpp"
@@ -2510,6 +2511,173 @@ int kano_k8s_pair_verdicts(kano_ctx* eg, kano_ctx* in, int flags, int64_t Q, con
 int kano_k8s_pair_verdicts_time(kano_ctx* eg, float* ms) {
   if (!eg || !ms) return -EINVAL;
   *ms = eg->kpair_ms;
+  return 0;
+}
+
+// K8sConnectivity.rule_usage: per entry the pairs it decides and passes, per
+// rule the pairs only it allows, over all n * n pairs from one walk of every
+// class list (k_usage_class, kano_k8s_usage.hpp).  Sources and codes are
+// checked as kano_k8s_pair_verdicts checks them; the work runs on eg's stream
+// and errors are reported on eg.
+int kano_k8s_rule_usage(kano_ctx* eg, kano_ctx* in, int flags, int64_t nids_e,
+                        const uint32_t* code_e, uint32_t np_level_e, const int32_t* group_e,
+                        int64_t nids_i, const uint32_t* code_i, uint32_t np_level_i,
+                        const int32_t* group_i, int64_t* decided_e, int64_t* passed_e,
+                        int64_t* sole_e, int64_t* decided_i, int64_t* passed_i, int64_t* sole_i,
+                        int64_t* tiers) {
+  const char* const what = "kano_k8s_rule_usage";
+  if (!eg || !in) return -EINVAL;
+  const std::string w(what);
+  kano_ctx* ctx = eg;
+  if (eg->device != in->device) return fail(eg, -EINVAL, w + ": contexts on two devices");
+  KCHK(hipSetDevice(eg->device));
+  KTRY(conn_source(eg, eg, what));
+  KTRY(conn_source(in, eg, what));
+  const i64 n = eg->n;
+  if (in->n != n) return fail(eg, -EINVAL, w + ": the two contexts must hold the same pods");
+  KTRY(conn_nids(eg, in, eg, what, nids_e, nids_i));
+  kano_ctx* const src[2] = {eg, in};
+  const uint32_t* const code[2] = {code_e, code_i};
+  const uint32_t np[2] = {np_level_e, np_level_i};
+  const i64 nids[2] = {nids_e, nids_i};
+  const int32_t* const group_in[2] = {group_e, group_i};
+  int64_t* const dec_out[2] = {decided_e, decided_i};
+  int64_t* const pas_out[2] = {passed_e, passed_i};
+  int64_t* const sole_out[2] = {sole_e, sole_i};
+  i64 live[2];
+  KTRY(tier_codes_check(eg, what, nids, code, np, live));
+  // the groups: non-decreasing in the id, from 0 on (NULL: every id its own)
+  std::vector<int32_t> group[2];
+  i64 ngroups[2];
+  for (int side = 0; side < 2; ++side) {
+    group[side].resize((size_t)nids[side]);
+    for (i64 p = 0; p < nids[side]; ++p) {
+      const int32_t g = group_in[side] ? group_in[side][p] : (int32_t)p;
+      if (g < (p ? group[side][p - 1] : 0))
+        return fail(eg, -EINVAL, w + ": " + (side ? "ingress" : "egress") + " group " +
+                                     std::to_string(p) + " is " + std::to_string(g) +
+                                     ": groups must be non-decreasing, from 0 on");
+      group[side][p] = g;
+    }
+    ngroups[side] = nids[side] ? (i64)group[side].back() + 1 : 0;
+  }
+  KTRY(conn_sync(eg, in, eg, what));
+  eg->kusage_ms = 0.f;
+  for (int side = 0; side < 2; ++side) {
+    if (dec_out[side]) std::fill(dec_out[side], dec_out[side] + nids[side], (int64_t)0);
+    if (pas_out[side]) std::fill(pas_out[side], pas_out[side] + nids[side], (int64_t)0);
+    if (sole_out[side]) std::fill(sole_out[side], sole_out[side] + ngroups[side], (int64_t)0);
+  }
+  if (tiers) std::fill(tiers, tiers + 16, (int64_t)0);
+  if (n == 0) return 0;
+  const int self = (flags & KANO_K8S_CONN_SELF) ? 1 : 0;
+  const bool has[2] = {conn_classes(eg), conn_classes(in)};
+  DBuf key[2], pk[2], olist[2], okey[2], ocnt[2], grp[2], size[2], cnt[2], scratch;
+  K8sUsageSide a[2];
+  size_t ncnt[2] = {0, 0}, nsize[2] = {0, 0};
+  KTRY(dalloc(ctx, scratch, sizeof(unsigned)));       // k_verdict_order's count, not read
+  for (int side = 0; side < 2; ++side) {
+    if (!has[side]) continue;
+    kano_ctx* s = src[side];
+    const size_t nnz = (size_t)std::max<i64>(1, s->nnz_sel), P = (size_t)nids[side];
+    KTRY(dalloc(ctx, key[side], sizeof(uint32_t) * P));
+    KTRY(dalloc(ctx, pk[side], sizeof(u64) * nnz));
+    KTRY(dalloc(ctx, olist[side], sizeof(int32_t) * nnz));
+    KTRY(dalloc(ctx, okey[side], sizeof(uint32_t) * nnz));
+    KTRY(dalloc(ctx, ocnt[side], sizeof(int32_t) * (size_t)s->rc.U));
+    KTRY(dalloc(ctx, grp[side], sizeof(int32_t) * P));
+    // size: the row classes' pods, then the column classes' (ldC * 64, the pad zero)
+    nsize[side] = (size_t)s->rc.U + (size_t)s->ldC * 64;
+    KTRY(dalloc(ctx, size[side], sizeof(int32_t) * nsize[side]));
+    // cnt: decided, passed, sole, tiers
+    ncnt[side] = 2 * P + (size_t)ngroups[side] + 8;
+    KTRY(dalloc(ctx, cnt[side], sizeof(ull) * ncnt[side]));
+    KCHK(hipMemcpyAsync(key[side].p, code[side], sizeof(uint32_t) * P, hipMemcpyHostToDevice,
+                        ctx->stream));
+    KCHK(hipMemcpyAsync(grp[side].p, group[side].data(), sizeof(int32_t) * P,
+                        hipMemcpyHostToDevice, ctx->stream));
+    K8sUsageSide& d = a[side];
+    d.U = s->rc.U;
+    d.soffc = P_<i64>(s->soffc);
+    d.olist = P_<int32_t>(olist[side]);
+    d.okey = P_<uint32_t>(okey[side]);
+    d.ocnt = P_<int32_t>(ocnt[side]);
+    d.np = np[side];
+    d.AC = P_<u64>(s->AC);
+    d.ldC = s->ldC;
+    d.group = P_<int32_t>(grp[side]);
+    d.rsize = P_<int32_t>(size[side]);
+    d.csize = d.rsize + s->rc.U;
+    d.decided = P_<ull>(cnt[side]);
+    d.passed = d.decided + P;
+    d.sole = d.passed + P;
+    d.tiers = d.sole + ngroups[side];
+  }
+  EventPair<> tev;
+  if (eg->stage_timing) KTRY(tev.start(ctx));
+  for (int side = 0; side < 2; ++side) {
+    if (!has[side]) continue;
+    kano_ctx* s = src[side];
+    const int32_t* rcls = P_<int32_t>(s->rc.cls);
+    const int32_t* ccls = P_<int32_t>(s->cc.cls);
+    KCHK(hipMemsetAsync(size[side].p, 0, sizeof(int32_t) * nsize[side], ctx->stream));
+    KCHK(hipMemsetAsync(cnt[side].p, 0, sizeof(ull) * ncnt[side], ctx->stream));
+    int32_t* rsize = P_<int32_t>(size[side]);
+    int wl;
+    i64 cap;
+    derived_shape(ctx, s->ldC, &wl, &cap);
+    // (a block counts 8 pods a lane or more before it adds its bins)
+    const dim3 hgrid((unsigned)std::min<i64>(nblk(n, (i64)TPB * 8), cap));
+    hipLaunchKernelGGL(k_usage_hist, hgrid, dim3(TPB), 0, ctx->stream, rcls, n, rsize, s->rc.U);
+    KLAUNCH();
+    hipLaunchKernelGGL(k_usage_hist, hgrid, dim3(TPB), 0, ctx->stream, ccls, n, rsize + s->rc.U,
+                       s->ldC * 64);
+    KLAUNCH();
+    hipLaunchKernelGGL(k_verdict_order, dim3((unsigned)std::min<i64>(s->rc.U, cap)), dim3(TPB), 0,
+                       ctx->stream, s->rc.U, (const i64*)P_<i64>(s->soffc),
+                       (const int32_t*)P_<int32_t>(s->slist),
+                       (const uint32_t*)P_<uint32_t>(key[side]), P_<u64>(pk[side]),
+                       P_<int32_t>(olist[side]), P_<uint32_t>(okey[side]), P_<int32_t>(ocnt[side]),
+                       P_<unsigned>(scratch));
+    KLAUNCH();
+    if (eg->kusage_grid > 0) cap = std::min<i64>(cap, eg->kusage_grid);
+    const i64 cpb = TPB / wl;
+    const dim3 grid((unsigned)std::min<i64>((s->rc.U + cpb - 1) / cpb, cap));
+    if (wl > 64) hipLaunchKernelGGL(k_usage_class<true>, grid, dim3(TPB), 0, ctx->stream, a[side], wl);
+    else hipLaunchKernelGGL(k_usage_class<false>, grid, dim3(TPB), 0, ctx->stream, a[side], wl);
+    KLAUNCH();
+    if (!self) continue;
+    hipLaunchKernelGGL(k_usage_self, dim3(nblk(n)), dim3(TPB), 0, ctx->stream, a[side], rcls, ccls,
+                       n);
+    KLAUNCH();
+  }
+  KTRY(tev.stop(ctx, &eg->kusage_ms));
+  std::vector<ull> host[2];
+  for (int side = 0; side < 2; ++side) {
+    if (!has[side]) continue;
+    host[side].resize(ncnt[side]);
+    KCHK(hipMemcpyAsync(host[side].data(), cnt[side].p, sizeof(ull) * ncnt[side],
+                        hipMemcpyDeviceToHost, ctx->stream));
+  }
+  KTRY(sync(ctx));
+  for (int side = 0; side < 2; ++side) {
+    if (!has[side]) {   // no class constrains anything: the whole domain is (default, allow)
+      if (tiers) tiers[side * 8] = n * n - (self ? n : 0);
+      continue;
+    }
+    const ull* h = host[side].data();
+    const i64 P = nids[side], G = ngroups[side];
+    if (dec_out[side]) std::copy(h, h + P, dec_out[side]);
+    if (pas_out[side]) std::copy(h + P, h + 2 * P, pas_out[side]);
+    if (sole_out[side]) std::copy(h + 2 * P, h + 2 * P + G, sole_out[side]);
+    if (tiers) std::copy(h + 2 * P + G, h + 2 * P + G + 8, tiers + side * 8);
+  }
+  return 0;
+}
+
+int kano_k8s_rule_usage_time(kano_ctx* eg, float* ms) {
+  if (!eg || !ms) return -EINVAL;
+  *ms = eg->kusage_ms;
   return 0;
 }
 

@@ -2367,6 +2367,7 @@ int kano_create(int device, kano_ctx** out) {
         if (k == "pvgrid" && v >= 0) ctx->verdict_grid = v;
         if (k == "kpf" && v >= 0 && v <= 2) ctx->kpair_form = v;
         if (k == "kpgrid" && v >= 0) ctx->kpair_grid = v;
+        if (k == "kugrid" && v >= 0) ctx->kusage_grid = v;
         if (k == "dgrid" && v >= 0) ctx->diff_grid = v;
         if (k == "ggrid" && v >= 0) ctx->group_grid = v;
         if (k == "gbatch" && v >= 0) ctx->group_batches = v;

@@ -307,6 +307,49 @@ class DeviceBuild:
                   "kano_k8s_pair_verdicts_time")
         return float(ms.value)
 
+    def k8s_rule_usage(self, ing: "DeviceBuild", allow_self: bool, code_e, np_level_e: int,
+                       code_i, np_level_i: int, group_e=None, group_i=None) -> dict:
+        """Per entry of the two builds the pairs of [0, n)^2 it decides and
+        passes, per group the pairs only it allows, under the rule of
+        k8s_pair_verdicts (kano_k8s_rule_usage); this context is the egress
+        build, ``ing`` the ingress build, codes and levels as there.
+        ``group_*``: an int32 per engine id, non-decreasing from 0 on (None:
+        every id its own group).  ``allow_self`` leaves the n self pairs out.
+        ``decided_*`` / ``passed_*`` (int64 per id), ``sole_*`` (int64 per
+        group) and ``tiers`` (int64[16]: per direction and tier its (allow,
+        deny) pairs)."""
+        ce = np.ascontiguousarray(np.asarray(code_e).reshape(-1), dtype=np.uint32)
+        ci = np.ascontiguousarray(np.asarray(code_i).reshape(-1), dtype=np.uint32)
+
+        def groups_of(group, code):
+            if group is None:
+                return None, len(code)
+            g = np.ascontiguousarray(np.asarray(group).reshape(-1), dtype=np.int32)
+            if g.shape != code.shape:
+                raise ValueError("one group per code expected")
+            return g, int(g[-1]) + 1 if len(g) and g[-1] >= 0 else 0
+
+        ge, ne = groups_of(group_e, ce)
+        gi, ni = groups_of(group_i, ci)
+        out = {"decided_e": np.zeros(len(ce), np.int64), "passed_e": np.zeros(len(ce), np.int64),
+               "sole_e": np.zeros(ne, np.int64), "decided_i": np.zeros(len(ci), np.int64),
+               "passed_i": np.zeros(len(ci), np.int64), "sole_i": np.zeros(ni, np.int64),
+               "tiers": np.zeros(16, np.int64)}
+        self._chk(self.lib.kano_k8s_rule_usage(
+            self.ctx, ing.ctx, 1 if allow_self else 0, int(ce.shape[0]), _ptr(ce),
+            int(np_level_e), _ptr(ge), int(ci.shape[0]), _ptr(ci), int(np_level_i), _ptr(gi),
+            _ptr(out["decided_e"]), _ptr(out["passed_e"]), _ptr(out["sole_e"]),
+            _ptr(out["decided_i"]), _ptr(out["passed_i"]), _ptr(out["sole_i"]),
+            _ptr(out["tiers"])), "kano_k8s_rule_usage")
+        return out
+
+    def k8s_rule_usage_time(self) -> float:
+        """The last k8s_rule_usage's device time (ms; KANO_TUNE=timing=1)."""
+        ms = ctypes.c_float(0.0)
+        self._chk(self.lib.kano_k8s_rule_usage_time(self.ctx, byref(ms)),
+                  "kano_k8s_rule_usage_time")
+        return float(ms.value)
+
     def path_shard_words(self) -> int:
         w = c_int64(0)
         self._chk(self.lib.kano_path_shard_words(self.ctx, byref(w)), "kano_path_shard_words")

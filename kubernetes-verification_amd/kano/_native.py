@@ -121,6 +121,10 @@ SIGNATURES = {
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p]),
     "kano_k8s_pair_verdicts_time": (c_int, [c_void_p, POINTER(c_float)]),
+    "kano_k8s_rule_usage": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_uint32,
+                                    c_void_p, c_int64, c_void_p, c_uint32, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "kano_k8s_rule_usage_time": (c_int, [c_void_p, POINTER(c_float)]),
     "kano_build_classes": (c_int, [c_void_p, c_int]),
     "kano_path_shard_words": (c_int, [c_void_p, POINTER(c_int64)]),
     "kano_path_shard": (c_int, [c_void_p, c_void_p]),

@@ -949,6 +949,41 @@ class K8sConnectivity:
         policies = self._policies if c.tiered else {"network": self._policies}
         return K8sPairVerdicts(r, c, policies)
 
+    def rule_usage(self) -> "K8sRuleUsage":
+        """Which rules do anything at all on this object's port, over every
+        ordered pod pair: per entry the pairs it decides and the pairs it
+        passes down, per NetworkPolicy rule the pairs only that rule allows
+        (kano_k8s_rule_usage: one walk of the class lists, exact counts, no
+        pair is enumerated).  With ``allow_self`` the n self pairs are left
+        out: they are allowed before any rule is read.  Reads only the two
+        full builds, so an object made with ``rows=`` answers the same.
+        "Dead" is per port: a rule dead at ``port=None`` can be live on a port
+        whose query drops the rule that shadows it."""
+        c = self._compiled
+        code_e, code_i = c.codes(self.port)
+        (group_e, rules_e), (group_i, rules_i) = rule_groups(c)
+        r = self.egress.engine.k8s_rule_usage(self.ingress.engine, self.allow_self, code_e,
+                                              c.np_level[0], code_i, c.np_level[1], group_e,
+                                              group_i)
+        policies = self._policies if c.tiered else {"network": self._policies}
+        return K8sRuleUsage(r, c, policies, (code_e, code_i), (group_e, group_i),
+                            (rules_e, rules_i))
+
+    def dead_rules(self, ports) -> List[tuple]:
+        """The rules that are dead on every port of ``ports`` (None or
+        (protocol, number) each): (direction, kind, policy name, rule index),
+        in rule order.  One ``on_port`` and one ``rule_usage`` per port.
+        Note: "dead" here means "counts on the port and still does nothing"
+        (``K8sRuleUsage.dead_rules``).  A rule that some port's query drops
+        decides nothing there either, but it is not dead there, so it is NOT
+        returned: list only ports on which the rules in question count."""
+        dead = None
+        for port in ports:
+            here = self.on_port(port).rule_usage().dead_rules()
+            also = set(here)
+            dead = here if dead is None else [r for r in dead if r in also]
+        return dead or []
+
 
 TIERS = ("default", "admin", "network", "baseline")
 _COUNT_KEYS = ("allowed", "self") + tuple(
@@ -1046,6 +1081,125 @@ class K8sPairDirection:
     def _name(self, what: str, q: int):
         p = int(getattr(self, what)[q])
         return None if p < 0 else self.entry(p)
+
+
+def rule_groups(compiled: Conformant):
+    """Per direction (egress, ingress): (group, rules) -- ``group`` an int32
+    per entry, one group per (kind, policy, rule) in entry order, and
+    ``rules`` per group (kind, policy index, rule index, action, first entry,
+    entries).  compile_conformant appends a rule's entries contiguously, so the
+    groups are non-decreasing (asserted: kano_k8s_rule_usage relies on it).
+    The entry of a NetworkPolicy that only isolates is a group of its own with
+    rule index None."""
+    out = []
+    for origin, tiers in ((compiled.origin_egress, compiled.tiers_egress),
+                          (compiled.origin_ingress, compiled.tiers_ingress)):
+        group = np.empty(len(origin), dtype=np.int32)
+        rules, seen, last = [], set(), None
+        for p, (org, (kind, level, action)) in enumerate(zip(origin, tiers)):
+            key = (kind, org[0], org[2])
+            if key != last:
+                assert key not in seen, f"the entries of rule {key} are not contiguous"
+                seen.add(key)
+                rules.append([kind, org[0], org[2], action, p, 0])
+                last = key
+            group[p] = len(rules) - 1
+            rules[-1][5] += 1
+        assert (np.diff(group) >= 0).all()
+        out.append((group, [tuple(r) for r in rules]))
+    return tuple(out)
+
+
+K8sRuleRecord = collections.namedtuple(
+    "K8sRuleRecord", "kind policy rule action on_port decided passed sole")
+
+
+class K8sRuleDirection:
+    """One direction of K8sRuleUsage: ``decided`` and ``passed`` (int64 per
+    entry of the direction's build) and ``sole`` (int64 per rule, in the order
+    of ``K8sRuleUsage.rules``; a rule = one group of ``group``)."""
+
+    def __init__(self, decided, passed, sole, group):
+        self.decided, self.passed, self.sole, self.group = decided, passed, sole, group
+
+
+class K8sRuleUsage:
+    """K8sConnectivity.rule_usage's result, counted over every ordered pod
+    pair (x, y) -- without the n self pairs when the object allows self
+    traffic -- per direction (``egress``: subject src, peer dst; ``ingress``:
+    subject dst, peer src), a K8sRuleDirection each.
+    ``counts``: per direction, tier and verdict the pairs decided there, named
+    as K8sPairVerdicts.counts names them (``egress_default_allow`` ..
+    ``ingress_baseline_deny``); a direction's eight sum to the pairs counted.
+    decided == 0 and passed == 0: the rule is dead -- removing it changes no
+    verdict on this port.  For a NetworkPolicy rule ``sole`` counts the pairs
+    that rule alone allows in its tier: removing the rule (the policy keeping
+    its types) denies exactly those pairs of that direction, so sole == 0 says
+    the rule is redundant; sole <= decided summed over the rule's entries."""
+
+    def __init__(self, r, compiled, policies, codes, groups, rules):
+        self.egress = K8sRuleDirection(r["decided_e"], r["passed_e"], r["sole_e"], groups[0])
+        self.ingress = K8sRuleDirection(r["decided_i"], r["passed_i"], r["sole_i"], groups[1])
+        self.counts = dict(zip(_COUNT_KEYS[2:], map(int, r["tiers"])))
+        self._policies = policies
+        self._records = {}
+        for direction, code, rl, np_level in (("egress", codes[0], rules[0], compiled.np_level[0]),
+                                              ("ingress", codes[1], rules[1],
+                                               compiled.np_level[1])):
+            d = getattr(self, direction)
+            G = len(rl)
+            dec = np.zeros(G, np.int64)
+            pas = np.zeros(G, np.int64)
+            np.add.at(dec, d.group, d.decided)
+            np.add.at(pas, d.group, d.passed)
+            recs = []
+            for g, (kind, pi, ri, action, first, cnt) in enumerate(rl):
+                if action == "Isolate":
+                    continue                    # not a rule: the policy's isolation alone
+                cd = int(code[first])
+                on_port = cd != 0xFFFFFFFF and (kind != "network" or cd == np_level * 4)
+                recs.append(K8sRuleRecord(kind, policies[kind][pi].name, ri, action, on_port,
+                                          int(dec[g]), int(pas[g]),
+                                          int(d.sole[g]) if kind == "network" else None))
+            self._records[direction] = recs
+
+    def _direction(self, direction):
+        if direction not in ("egress", "ingress"):
+            raise ValueError(f"direction must be 'egress' or 'ingress', not {direction!r}")
+        return self._records[direction]
+
+    def rules(self, direction: str) -> List[K8sRuleRecord]:
+        """One record per compiled rule of ``direction``, in entry order:
+        (kind, policy name, rule index, action, on_port, decided, passed,
+        sole).  ``on_port`` is False for a rule the port's query drops;
+        ``sole`` is None outside the NetworkPolicy tier.  The entries that only
+        isolate are not rules and are not listed, nor are rules without a
+        compiled entry (ipBlock-only peers, selectors no pod can meet)."""
+        return list(self._direction(direction))
+
+    def blame(self, direction: str, deny_only: bool = True) -> Dict[tuple, int]:
+        """{(kind, policy name, rule index): the pairs that rule decided} in
+        ``direction``, over the whole domain -- what K8sPairVerdicts.blame
+        returns for all pairs; ``deny_only``: the Deny rules only."""
+        out: Dict[tuple, int] = {}
+        for r in self._direction(direction):
+            if r.decided and (r.action == "Deny" or not deny_only):
+                key = (r.kind, r.policy, r.rule)
+                out[key] = out.get(key, 0) + r.decided
+        return out
+
+    def dead_rules(self) -> List[tuple]:
+        """The rules that count on the port and decide and pass nothing:
+        (direction, kind, policy name, rule index)."""
+        return [(d, r.kind, r.policy, r.rule) for d in ("egress", "ingress")
+                for r in self._records[d] if r.on_port and not r.decided and not r.passed]
+
+    def redundant_rules(self) -> List[tuple]:
+        """The NetworkPolicy rules with sole == 0, dead ones and the rules the
+        port drops included: removing one of them alone changes no verdict on
+        this port.  (direction, kind, policy name, rule index)."""
+        return [(d, r.kind, r.policy, r.rule) for d in ("egress", "ingress")
+                for r in self._records[d] if r.kind == "network" and r.sole == 0]
 
 
 def _connect(egress, ingress, compiled, policies, port, allow_self, isolated, device, rows,

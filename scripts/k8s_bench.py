@@ -201,6 +201,44 @@ def conn_tiers(args, n, pods, pols, nss, rows):
             "ingress_isolated": info["ingress_isolated"]}
 
 
+def usage_times(args, n, pods, pols, nss):
+    """--usage: K8sConnectivity.rule_usage on the cluster (with the generated
+    admin and baseline policies of --admin / --baseline): its call time, its
+    device time and, beside it, kano_k8s_conn_tiers' whole device time on the
+    same builds (``conn_tiers_whole_device_ms``: the order and class kernels,
+    which walk the same lists, plus the transpose, the expansion and the
+    matrix write -- the class step alone is read off a kernel trace, see
+    DESIGN.md).  Up to 4000 pods also the route through pair_verdicts over all
+    n * n pairs, whose blame must equal rule_usage's."""
+    import numpy as np
+    from kano import k8s
+    admin, base = admin_policies(args.admin, args.baseline, len(nss))
+    conn = k8s.connectivity(pods, pols, nss, allow_self=False, admin=admin, baseline=base)
+    out = {"conn_tiers_whole_device_ms": round(conn.allowed._engine.k8s_conn_time(), 4)}
+    best = None
+    for _ in range(args.reps):
+        t = time.perf_counter()
+        u = conn.rule_usage()
+        r = (time.perf_counter() - t, conn.egress.engine.k8s_rule_usage_time())
+        best = r if best is None or r[1] < best[1] else best
+    out.update(rule_usage_ms=round(best[0] * 1e3, 3), rule_usage_device_ms=round(best[1], 4),
+               egress_entries=len(conn.origin_egress), ingress_entries=len(conn.origin_ingress),
+               dead_rules=len(u.dead_rules()), redundant_rules=len(u.redundant_rules()),
+               counts=u.counts)
+    if n <= 4000:
+        pr = np.stack(np.meshgrid(np.arange(n), np.arange(n), indexing="ij"), -1)
+        pr = pr.reshape(-1, 2).astype(np.int32)
+        t = time.perf_counter()
+        v = conn.pair_verdicts(pr)
+        blames = {d: v.blame(d, False) for d in ("egress", "ingress")}
+        out["all_pairs_route_ms"] = round((time.perf_counter() - t) * 1e3, 3)
+        out["all_pairs_device_ms"] = round(conn.egress.engine.k8s_pair_verdicts_time(), 4)
+        for d, b in blames.items():
+            assert b == u.blame(d, False), f"{d}: rule_usage and pair_verdicts disagree"
+        out["blame_equal"] = True
+    return out
+
+
 HBM_SPEC = 8.0e12   # MI355X HBM3E, bytes per second
 
 
@@ -253,6 +291,8 @@ def conn(args):
             tiers["pair_verdicts"] = pair_times(args, n, te, ti, c.codes(None), c.np_level)
         if args.admin > 0 or args.baseline:
             tiers["tiers"] = conn_tiers(args, n, pods, pols, nss, rows)
+        if args.usage:
+            tiers["rule_usage"] = usage_times(args, n, pods, pols, nss)
         print(json.dumps({
             "workload": "k8s.connectivity (conformant reading), synthetic K8s cluster",
             "form": args.conn_form,
@@ -286,6 +326,9 @@ def main():
     ap.add_argument("--pairs", type=int, default=0,
                     help="--conn: also time K8sConnectivity.pair_verdicts' call on this many "
                          "random pairs (with --admin / --baseline: over the tiered builds too)")
+    ap.add_argument("--usage", action="store_true",
+                    help="--conn: also time K8sConnectivity.rule_usage (with --admin / --baseline: "
+                         "over the tiered cluster); up to 4000 pods against the all-pairs route")
     ap.add_argument("--pods", type=int, nargs="+", default=[10000, 100000])
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--form", default="classes", choices=["classes", "pods"])
